@@ -1,7 +1,19 @@
 #!/usr/bin/env python3
 """gpbs headline benchmark (driver contract).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: the solo
+rates of the headline mix's tenants, then ONE timed gpbs co-run of W warm-up
+and K timed step windows; ``value`` is that run's aggregate and
+``ms_per_step`` its wall time over K.  ``--full`` adds everything else
+described below: 5 randomized repetitions (``value`` = their median), the
+comparison policies and ablations, the extra mixes, the CU-mask layout check,
+the GPU clock / power record and the solo rates measured again after the
+runs; a mix after the headline that would end past ``--budget-s`` (540 s
+after the start) is left out.  ``--dump-outputs DIR`` writes what the
+tenants of the headline mix computed in the last timed run to
+``DIR/<tenant>.npy`` (see dump_outputs).
 
 Runs the BASELINE.json metric -- co-run slowdown vs solo + aggregate
 throughput of the 4-tenant mix (MFMA GEMM + HBM stream + all-reduce + idle)
@@ -14,14 +26,16 @@ when its one-unit self-test fails).  Rank 0 prints ONE JSON line.
 ``value`` = aggregate normalized throughput of the headline mix summed over
 all GPUs (sum over throughput tenants of co-run rate / solo rate,
 "solo-equivalents"; higher is better).  Solo rates are measured with the
-same steady protocol as the co-run (backlogged, W + K windows, alone).
-Comparison policies run on the same box, 5 randomized reps each: none
+same steady protocol as the co-run (backlogged, W + K windows, alone; a
+plain run times at most 20 solo windows per tenant, so its set-up does not
+grow with K).
+With --full, comparison policies run on the same box, 5 randomized reps each: none
 (default hardware sharing), static (equal XCD split), static-se (the
 hand-picked shader-engine layout, no engine, no counters), the PBS ablations
 (credit-fixed*: fixed quantum; gpbs-split: crowded class regions split by
 XCD blocks instead of time-shared) and gpbs-lat (latency hold).
 
-By default two more mixes run after the headline and are reported under
+With --full, more mixes run after the headline and are reported under
 ``mixes``: "phase" (a tenant alternating GEMM <-> stream every 300 ms and a
 stream tenant stopping / starting every 500 ms: the counter-driven layout
 must follow, a static one cannot) and "8mix" (config #4's 8 tenants on one
@@ -34,7 +48,9 @@ import argparse
 import json
 import os
 import sys
+import time
 
+T_START = time.monotonic()
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 # one HW queue per tenant/scheduler stream (see pbs_amd/runtime/gpu.py)
@@ -116,17 +132,67 @@ def mix_summary(mix, runs, solo, reps):
     return out
 
 
+DUMP_SAMPLE = 1 << 20  # elements kept per output (4 tenants x 4 MiB of float32)
+DUMP_SEED = 20261019
+
+
+def dump_outputs(corun, outdir):
+    """--dump-outputs: what the mix's tenants computed in the last timed run,
+    one ``<tenant>.npy`` (float32) per native runner -- the GEMM's C, the
+    stream copy's destination, the reduce-copy's sum, the GEMV's y.  The
+    inputs are seeded per tenant (runtime/gpu.py Runner) and every unit of a
+    tenant writes the same values, so two builds must agree file for file.
+    An output of more than DUMP_SAMPLE elements is stored as a fixed sample:
+    the elements at DUMP_SAMPLE sorted indexes drawn with seed DUMP_SEED
+    (the same for every run of a given size).  The tensors are found through
+    the runners' ABI records, so this file runs as it is on an older tree of
+    the package (comparing two builds).  A tenant whose buffers a
+    collective owns (the N > 1 all-reduce) is skipped: what it holds depends
+    on how many units ran."""
+    import numpy as np
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()
+    for name, r in corun.runners.items():
+        # a native runner's output: the tensor its ABI record names as c (alt_c
+        # for a phase tenant's second workload) among the buffers it holds
+        cfg, bufs = getattr(r, "cfg", None), getattr(r, "buffers", None) or []
+        for suffix, ptr in (("", getattr(cfg, "c", None)), ("_alt", getattr(cfg, "alt_c", None))):
+            t = next((b for b in bufs if ptr and b.data_ptr() == ptr), None)
+            if t is None:
+                continue
+            flat = t.reshape(-1)
+            if flat.numel() > DUMP_SAMPLE:
+                g = torch.Generator().manual_seed(DUMP_SEED)
+                idx = torch.randint(flat.numel(), (DUMP_SAMPLE,), generator=g, dtype=torch.int64).sort().values
+                flat = flat[idx.to(flat.device)]
+            np.save(os.path.join(outdir, f"{name}{suffix}.npy"), flat.float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: --reps 5, the comparison policies and ablations of "
+                         "every mix (--mix all), the CU-mask layout check, the GPU clock / power record and the "
+                         "solo rates measured again after the runs; off: one gpbs run of the headline mix")
+    ap.add_argument("--budget-s", type=float, default=540.0,
+                    help="with several mixes: a mix after the headline is left out when it would end more than this "
+                         "many seconds after the start (0: no budget)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the headline mix's tenants computed in the last timed run to DIR/<tenant>.npy "
+                         "(float32; large outputs as a fixed seeded sample)")
     ap.add_argument("--policies", default="",
-                    help="comma list for the headline mix (default: per-mix list below); gpbs is the reported policy")
+                    help="comma list for the headline mix (default: gpbs alone; with --full the per-mix list "
+                         "below); gpbs is the reported policy")
     ap.add_argument("--keep-engines", action="store_true",
                     help="one engine per policy for the whole process (default: a fresh engine per timed run)")
-    ap.add_argument("--reps", type=int, default=5,
-                    help="timed runs per policy, in a randomized order per repetition (median and IQR reported)")
+    ap.add_argument("--reps", type=int, default=None,
+                    help="timed runs per policy, in a randomized order per repetition (median and IQR reported; "
+                         "default 1, with --full 5)")
     ap.add_argument("--seed", type=int, default=20261016, help="policy-order shuffle seed (same on every rank)")
     ap.add_argument("--target-ms", type=float, default=30.0)
     ap.add_argument("--protocol", default="steady", choices=["steady", "quota"],
@@ -144,14 +210,14 @@ def main():
     ap.add_argument("--coll", default="ipc", choices=["ipc", "rccl"],
                     help="N > 1 all-reduce tenant: ipc (gated gpbs kernel over IPC-mapped peer buffers, xGMI; "
                          "default) or rccl (torch.distributed all-reduce, not CU-confined)")
-    ap.add_argument("--resolo", dest="resolo", action="store_true", default=True,
+    ap.add_argument("--resolo", dest="resolo", action="store_true", default=None,
                     help="measure the solo rates again after each mix's runs (reported as "
                          "solo._end_over_start_rate, not used): a GPU that got slower over the runs shows here "
-                         "(default on)")
+                         "(default on with --full)")
     ap.add_argument("--no-resolo", dest="resolo", action="store_false")
     ap.add_argument("--out", default="")
     ap.add_argument("--no-cu-check", dest="cu_check", action="store_false",
-                    help="skip the CU-mask layout check (scripts/cu_map_check.py) run before the bench")
+                    help="with --full: skip the CU-mask layout check (scripts/cu_map_check.py) run before the bench")
     ap.add_argument("--rehearse-ipc", action="store_true",
                     help="like --rehearse (every rank on GPU 0, gloo) but with the gated IPC all-reduce tenant on "
                          "the GPU: rehearses the whole N > 1 path (IPC self-test, P2P-flag barrier, gang epochs, "
@@ -163,8 +229,9 @@ def main():
                     help="PBS metric source: live CDNA4 hardware counters (rocprofiler-sdk device counting, "
                          "attributed to tenants by shader-engine ownership; default), or the modeled per-tile "
                          "counters of the tenant kernels (debug cross-check)")
-    ap.add_argument("--mix", default="all", choices=["all", "4mix", "gemm2", "phase", "phase-ts", "8mix", "slo", "llm5"],
-                    help="all (default): 4mix (headline, BASELINE config #3) + phase (phase-changing mix) + "
+    ap.add_argument("--mix", default=None, choices=["all", "4mix", "gemm2", "phase", "phase-ts", "8mix", "slo", "llm5"],
+                    help="default: 4mix alone, with --full all; "
+                         "all: 4mix (headline, BASELINE config #3) + phase (phase-changing mix) + "
                          "phase-ts (the phase mix with a time-shared memory region, where the adaptive quantum "
                          "matters) + 8mix (config #4's 8 tenants on one GPU); gemm2: config #2 (two 4096^2 GEMM "
                          "tenants); "
@@ -184,6 +251,26 @@ def main():
                     help="diagnostics: dump every thread's stack every this many seconds (0: off)")
     ap.add_argument("--llm5-warm-s", type=float, default=5.0, help="--mix llm5: untimed warm-up seconds")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    # a plain run: one gpbs run of the headline mix; --full: the whole study
+    if args.reps is None:
+        args.reps = 5 if args.full or args.mix == "llm5" else 1  # config #5 is a study of its own
+    if args.mix is None:
+        args.mix = "all" if args.full else "4mix"
+    if args.resolo is None:
+        args.resolo = args.full
+    # a tree this user cannot write (built by another user): run on the
+    # libraries build() left there -- no rebuild check, no build lock
+    libdir = os.path.join(ROOT, "pbs_amd", "lib")
+    prebuilt = not os.access(libdir if os.path.isdir(libdir) else os.path.dirname(libdir), os.W_OK)
+    if prebuilt:
+        core, hip = (os.path.join(libdir, n) for n in ("libgpbs.so", "libgpbs_hip.so"))
+        if not (os.path.exists(core) and os.path.exists(hip)):
+            print(f"bench.py: {libdir} holds no built libraries and is not writable: build the tree first",
+                  file=sys.stderr)
+            sys.exit(2)
+        os.environ.setdefault("GPBS_CORE_LIB", core)  # pbs_amd/_native.py: load this, build nothing
     if args.mix == "llm5":  # its own process tree (daemon + torch tenants); nothing here touches HIP first
         return run_llm5(args)
     if args.hang_dump_s > 0:  # diagnostics: every thread's stack when a run stops progressing
@@ -211,7 +298,7 @@ def main():
     # rank's device in a child process before this one touches the GPU
     # (scripts/cu_map_check.py; a rehearsal checks once, on rank 0)
     cu_map = None
-    if args.cu_check and (not args.rehearse or rank == 0):
+    if args.full and args.cu_check and (not args.rehearse or rank == 0):
         import subprocess
         try:
             p = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "cu_map_check.py"), "--device", str(local)],
@@ -244,11 +331,12 @@ def main():
             counters = "model"
     # the GPU's clock / power / temperature / throttle residency over every
     # timed run (host thread, amdsmi or sysfs): tells a DVFS / power-state
-    # drift from a queue / pipe effect
+    # drift from a queue / pipe effect (--full)
     from pbs_amd.utils.gpustate import GpuStateRecorder, bdf_mismatch, device_bdf
     bdf = device_bdf(local)
-    gpustate = GpuStateRecorder(bdf, period_s=0.2).start()
-    rank_diag = {"rank": rank, "local_rank": local, "device_bdf": bdf, "gpu_state_source": gpustate.source,
+    gpustate = GpuStateRecorder(bdf, period_s=0.2).start() if args.full else None
+    rank_diag = {"rank": rank, "local_rank": local, "device_bdf": bdf,
+                 "gpu_state_source": gpustate.source if gpustate else None,
                  "counters": counters, "cu_map_ok": cu_map.get("ok") if cu_map else None}
     if counters == "hw":
         rank_diag["hwc_agent"] = hwc.agent()
@@ -282,7 +370,7 @@ def main():
             sys.exit(3)
 
     from pbs_amd import build
-    if rank == 0:  # one builder per node; the others wait (no concurrent relink)
+    if rank == 0 and not prebuilt:  # one builder per node; the others wait (no concurrent relink)
         build.build_all()
     if world > 1:
         dist.barrier(group=groups["ctrl"])
@@ -325,7 +413,9 @@ def main():
                           protocol=args.protocol, step_ms=args.step_ms, gang_transport=args.gang_transport,
                           gang_shm_base=f"{gang_base}-{mix}" if gang_base else "",
                           gang_wait_driven=args.gang_wait_driven, fresh_engine=not args.keep_engines,
-                          coll_impl=args.coll, kernel_trace=args.kernel_trace and counters == "hw")
+                          coll_impl=args.coll, kernel_trace=args.kernel_trace and counters == "hw",
+                          # a plain run's set-up must not grow with --steps: at most 20 timed solo windows
+                          solo_steps=0 if args.full else min(args.steps, 20))
         if args.rehearse:
             cfg.coll_bytes = 4 << 20  # CPU gloo all-reduce stand-in
         c = Corun(cfg, rank=rank, world=world, device=local, groups=groups, log=log,
@@ -341,6 +431,8 @@ def main():
             order += perm
         for p in order:
             runs[p].append(c.run_policy(p, args.steps, args.warmup))
+        if args.dump_outputs and mix == mixes[0] and rank == 0:
+            dump_outputs(c, args.dump_outputs)
         solo = c.solo_report()
         if args.resolo:  # diagnostic: the solo rates again after the runs (drift over the mix)
             start = dict(c.solo_unit_ms)
@@ -370,6 +462,7 @@ def main():
         return runs, order, solo
 
     results = {}
+    spent_s, spent_cost = 0.0, 0
     for mix in mixes:
         # crowded mixes (phase-ts, 8mix, slo) carry the long-quantum
         # ablations on the flagship's layout: one 30 ms
@@ -382,11 +475,27 @@ def main():
                    "phase-ts": "none,static-se,credit-fixed-ts30,credit-classq-f,atc,gpbs-ts,gpbs",
                    "8mix": "none,static-se,credit-fixed-ts30,credit-classq-f,gpbs-split,atc,gpbs-ts,gpbs",
                    "slo": "none,static-se,credit-fixed-ts30,credit-classq-f,atc,gpbs-ts,gpbs"}[mix]
-        spec = args.policies if (args.policies and mix == mixes[0]) else default
+        spec = args.policies if (args.policies and mix == mixes[0]) else default if args.full else "gpbs"
         pols = tuple(p for p in spec.split(",") if p)
         reps = args.reps if mix == mixes[0] else args.reps_extra
+        # time budget: a mix after the headline is left out (and said so on
+        # stderr) when, at the rate of the mixes run so far, it would end past
+        # --budget-s; a run costs one unit, a tenant's solo windows one each
+        cost = len(pols) * max(1, reps) + len(MIXES[mix]["throughput"]) * (2 if args.resolo else 1)
+        if mix != mixes[0] and args.budget_s > 0:
+            left = args.budget_s - (time.monotonic() - T_START)
+            if world > 1:  # every rank must decide alike
+                t = torch.tensor([left], dtype=torch.float64)
+                dist.all_reduce(t, op=dist.ReduceOp.MIN, group=groups["ctrl"])
+                left = float(t.item())
+            if 1.25 * cost * spent_s / spent_cost > left:
+                log(f"bench.py: mix {mix} left out: {left:.0f} s of --budget-s {args.budget_s:.0f} left")
+                continue
+        t_mix = time.monotonic()
         runs, order, solo = run_mix(mix, pols, reps)
+        spent_s, spent_cost = spent_s + time.monotonic() - t_mix, spent_cost + cost
         results[mix] = {"runs": runs, "order": order, "summary": mix_summary(mix, runs, solo, reps)}
+    mixes = [m for m in mixes if m in results]
 
     head = mixes[0]
     hs = results[head]["summary"]
@@ -448,7 +557,8 @@ def main():
     else:
         allr = [rank_diag]
     line["ranks"] = allr
-    gpustate.stop()
+    if gpustate is not None:
+        gpustate.stop()
     if rank == 0:
         # the detail record (every policy table, per-tenant rows, ranks, GPU
         # state) goes to --out; stdout gets the compact contract line, last

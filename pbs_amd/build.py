@@ -132,17 +132,26 @@ def _compile_parallel(jobs, verbose):
 
 
 def build_core(verbose=False, sanitize: str | None = None):
-    """Build libgpbs.so.  sanitize in {None, 'address', 'thread', 'undefined'}."""
+    """Build libgpbs.so.  sanitize in {None, 'address', 'thread', 'undefined'}.
+    An up-to-date library is returned without taking the lock or writing
+    anything: a user who cannot write the tree (it was built by another)
+    loads what is there."""
+    target, _, deps = _core_plan(sanitize)
+    if not _lib_stale(target, deps, str(sanitize)):
+        return target
     with _BuildLock():
         return _build_core(verbose, sanitize)
 
 
-def _build_core(verbose=False, sanitize: str | None = None):
-    os.makedirs(LIBDIR, exist_ok=True)
+def _core_plan(sanitize):
     srcs = _srcs(CORE_DIRS, [".cpp"])
     name = "libgpbs.so" if not sanitize else f"libgpbs_{sanitize}.so"
-    target = os.path.join(LIBDIR, name)
-    deps = srcs + _headers() + [__file__]
+    return os.path.join(LIBDIR, name), srcs, srcs + _headers() + [__file__]
+
+
+def _build_core(verbose=False, sanitize: str | None = None):
+    os.makedirs(LIBDIR, exist_ok=True)
+    target, srcs, deps = _core_plan(sanitize)
     if not _lib_stale(target, deps, str(sanitize)):
         return target
     objdir = os.path.join(ROOT, "build", "core" + (("_" + sanitize) if sanitize else ""))
@@ -175,17 +184,24 @@ def hipcc():
 def build_hip(verbose=False):
     """Build libgpbs_hip.so for gfx950 (cross-compiles without a GPU)."""
     core = build_core(verbose)
+    target, srcs, _, deps = _hip_plan()
+    if srcs and not _lib_stale(target, deps, ARCH):  # up to date: no lock, nothing written
+        return target
     with _BuildLock():
         return _build_hip(verbose)
 
 
-def _build_hip(verbose=False):
+def _hip_plan():
     srcs = _srcs([HIP_DIR], [".hip", ".cpp"])
-    if not srcs:
-        return None
-    target = os.path.join(LIBDIR, "libgpbs_hip.so")
     hdrs = _headers() + sorted(glob.glob(os.path.join(CSRC, HIP_DIR, "*.hpp")))
     deps = srcs + hdrs + [__file__] + _srcs(CORE_DIRS, [".cpp"]) + _headers()
+    return os.path.join(LIBDIR, "libgpbs_hip.so"), srcs, hdrs, deps
+
+
+def _build_hip(verbose=False):
+    target, srcs, hdrs, deps = _hip_plan()
+    if not srcs:
+        return None
     if not _lib_stale(target, deps, ARCH):
         return target
     objdir = os.path.join(ROOT, "build", "hip")

@@ -23,6 +23,6 @@ rc = L.gpbs_hip_hwc_attr_selftest(11, 200, C.byref(worst))
 print(f"hwc_attr_selftest rc={rc} max_rel={worst.value:.3g}", flush=True)
 import bench  # noqa: E402
 
-sys.argv = ["bench.py", "--mix", "4mix", "--policies", "none,gpbs", "--reps", "1", "--steps", "20", "--warmup", "3",
+sys.argv = ["bench.py", "--full", "--mix", "4mix", "--policies", "none,gpbs", "--reps", "1", "--steps", "20", "--warmup", "3",
             "--counters", "model", "--out", os.path.join(ROOT, "gpurun_out", "prof_r3_bench.json")]
 bench.main()
