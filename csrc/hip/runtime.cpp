@@ -41,12 +41,15 @@ using namespace gpbs_hip;
 extern "C" {
 int gpbs_adapt_update(gpbs_adapt_state_t*, const gpbs_adapt_params_t*, uint64_t, uint64_t, uint64_t, uint64_t);
 int gpbs_hip_gemm_units(int, int);
+int gpbs_hip_gemm_fp8_units(int, int);
 int gpbs_hwc_sample(uint64_t* out, int nxcd);
 int gpbs_hwc_sample_se(uint64_t* se_out, uint64_t* x_out);
 int gpbs_hwc_slot_per_se(int k);
 int gpbs_hwc_active(void);
 int gpbs_hip_gemm_bf16(const void*, const void*, void*, int, int, int, void*, const void*, unsigned, unsigned, void*,
                        void*, int, hipStream_t);
+int gpbs_hip_gemm_fp8(const void*, const float*, const void*, const float*, void*, int, int, int, int, void*, const void*,
+                      unsigned, unsigned, void*, void*, int, hipStream_t);
 int gpbs_hip_stream_copy(const void*, void*, unsigned long long, unsigned, void*, const void*, unsigned, unsigned,
                          void*, void*, int, hipStream_t);
 int gpbs_hip_reduce_bf16(const void*, const void*, void*, unsigned long long, unsigned, void*, const void*, unsigned,
@@ -1505,7 +1508,11 @@ int ctr_adapt_harvest(void* user, int max, int* tenants_out, gpbs_adapt_state_t*
 
 // --------------------------------------------------------------------- runner
 
-enum Kind { K_GEMM = 1, K_STREAM = 2, K_REDUCE = 3, K_GEMV = 4, K_ALLREDUCE = 5 };
+enum Kind { K_GEMM = 1, K_STREAM = 2, K_REDUCE = 3, K_GEMV = 4, K_ALLREDUCE = 5, K_GEMM_FP8 = 6 };
+// K_GEMM_FP8 operands: a = Aq (M*K e4m3 bytes) then sa (M floats) in one
+// allocation, b = Bq (N*K bytes) then sb (N floats); K % 128 keeps the
+// scales 4-byte aligned.  Compute class like K_GEMM: grid choice and hold
+// treat every kind but K_GEMV alike, so it needs no branch of its own there.
 
 // ---- all-reduce tenant over IPC-mapped peer buffers (coll_kernels.hip) ----
 // Host mirror of the device CollDesc: per rank its input, output and flag
@@ -1926,6 +1933,7 @@ struct Runner {
         return hi > lo ? (u32)((hi - lo + chunk8 - 1) / chunk8) : 0u;
       }
       case K_GEMM: return (u32)gpbs_hip_gemm_units(w.M, w.N);
+      case K_GEMM_FP8: return (u32)gpbs_hip_gemm_fp8_units(w.M, w.N);
       case K_STREAM:
       case K_REDUCE: return (u32)((w.bytes + w.chunk - 1) / w.chunk);
       case K_GEMV: return (u32)((w.M + 15) / 16);
@@ -2050,6 +2058,11 @@ struct Runner {
       case K_GEMM:
         return gpbs_hip_gemm_bf16(w.a, w.b, w.c, w.M, w.N, w.K, q, tab, mode, me, ctx->d_cnt, &h_status[qi], grid,
                                   stream);
+      case K_GEMM_FP8: {
+        const char *aq = (const char*)w.a, *bq = (const char*)w.b;
+        return gpbs_hip_gemm_fp8(aq, (const float*)(aq + (size_t)w.M * w.K), bq, (const float*)(bq + (size_t)w.N * w.K),
+                                 w.c, w.M, w.N, w.K, 0, q, tab, mode, me, ctx->d_cnt, &h_status[qi], grid, stream);
+      }
       case K_STREAM:
         return gpbs_hip_stream_copy(w.a, w.c, w.bytes, (unsigned)w.chunk, q, tab, mode, me, ctx->d_cnt,
                                     &h_status[qi], grid, stream);
@@ -3845,6 +3858,8 @@ void* gpbs_runner_create(void* ctx, const gpbs_runner_cfg_t* cfg) {
   if ((cfg->kind == K_STREAM || cfg->kind == K_REDUCE) && (cfg->bytes % 16 || cfg->chunk_bytes <= 0 || cfg->chunk_bytes % 16))
     return nullptr;
   if (cfg->kind == K_GEMV && cfg->K % 512) return nullptr;
+  if (cfg->kind == K_GEMM_FP8 && (cfg->M <= 0 || cfg->N <= 0 || cfg->K <= 0 || cfg->M % 128 || cfg->N % 128 || cfg->K % 128))
+    return nullptr;
   if (cfg->kind == K_ALLREDUCE &&
       (!cfg->a || cfg->M < 1 || cfg->M > kCollMax || cfg->N < 0 || cfg->N >= cfg->M || cfg->bytes % (16ull * cfg->M) ||
        cfg->chunk_bytes <= 0 || cfg->chunk_bytes % 16))
@@ -3854,7 +3869,10 @@ void* gpbs_runner_create(void* ctx, const gpbs_runner_cfg_t* cfg) {
       (cfg->alt_bytes % 16 || cfg->alt_chunk_bytes <= 0 || cfg->alt_chunk_bytes % 16))
     return nullptr;
   if (cfg->alt_kind == K_GEMV && cfg->alt_K % 512) return nullptr;
-  if (cfg->alt_kind < 0 || cfg->alt_kind > K_GEMV) return nullptr;
+  if (cfg->alt_kind == K_GEMM_FP8 &&
+      (cfg->alt_M <= 0 || cfg->alt_N <= 0 || cfg->alt_K <= 0 || cfg->alt_M % 128 || cfg->alt_N % 128 || cfg->alt_K % 128))
+    return nullptr;
+  if (cfg->alt_kind < 0 || (cfg->alt_kind > K_GEMV && cfg->alt_kind != K_GEMM_FP8)) return nullptr;
   hipSetDevice(c->device);
   for (int have = c->cnt_rows.load(); have < cfg->tenant + 1 && !c->cnt_rows.compare_exchange_weak(have, cfg->tenant + 1);) {
   }

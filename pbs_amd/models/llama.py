@@ -134,13 +134,15 @@ class Block(nn.Module):
             "w2": llm.Fp8Weight(self.w2.weight),
         }
 
-    def forward_fp8(self, x, cos, sin, cache, pos: int):
+    def forward_fp8(self, x, cos, sin, cache, pos: int, tiled: bool = False):
         """Decode/prefill block on fp8 weights (fp8 MFMA linears + fused gfx950
-        RMSNorm/RoPE/SwiGLU); inference only."""
+        RMSNorm/RoPE/SwiGLU); inference only.  ``tiled``: the linears run the
+        LDS-tiled fp8 GEMM (one launch for any M) where their N allows it."""
         from ..ops import llm
         cfg, hd, f = self.cfg, self.cfg.head_dim, self._fp8
         B, S, _ = x.shape
-        qkv = llm.fp8_linear_q(*llm.rmsnorm_quant_fp8(x, self.attn_norm.weight, self.attn_norm.eps), f["qkv"])
+        qkv = llm.fp8_linear_q(*llm.rmsnorm_quant_fp8(x, self.attn_norm.weight, self.attn_norm.eps), f["qkv"],
+                               tiled=tiled)
         nq, nkv = cfg.n_heads * hd, cfg.n_kv_heads * hd
         q = qkv[..., :nq].reshape(B, S, cfg.n_heads, hd)
         k = qkv[..., nq:nq + nkv].reshape(B, S, cfg.n_kv_heads, hd)
@@ -151,9 +153,10 @@ class Block(nn.Module):
         vc[:, :, pos:pos + S] = v.transpose(1, 2)
         o = F.scaled_dot_product_attention(q.transpose(1, 2), kc[:, :, :pos + S], vc[:, :, :pos + S],
                                            is_causal=(S > 1), enable_gqa=True)
-        x = x + llm.fp8_linear(o.transpose(1, 2).reshape(B, S, nq), f["o"])
-        gu = llm.fp8_linear_q(*llm.rmsnorm_quant_fp8(x, self.mlp_norm.weight, self.mlp_norm.eps), f["w13"])
-        return x + llm.fp8_linear_q(*llm.swiglu_quant_fp8(gu), f["w2"])
+        x = x + llm.fp8_linear(o.transpose(1, 2).reshape(B, S, nq), f["o"], tiled=tiled)
+        gu = llm.fp8_linear_q(*llm.rmsnorm_quant_fp8(x, self.mlp_norm.weight, self.mlp_norm.eps), f["w13"],
+                              tiled=tiled)
+        return x + llm.fp8_linear_q(*llm.swiglu_quant_fp8(gu), f["w2"], tiled=tiled)
 
     def decode_fp8_static(self, x, cos, sin, cache, pos_i32, pos_i64, mask):
         """One-token decode with every shape static and the position on device
@@ -230,15 +233,16 @@ class Llama(nn.Module):
         self._fp8_head = llm.Fp8Weight(self.lm_head.weight)
         return self
 
-    def forward_fp8(self, tokens, cache, pos: int = 0, last_only: bool = False):
+    def forward_fp8(self, tokens, cache, pos: int = 0, last_only: bool = False, tiled: bool = False):
         from ..ops import llm
         cos, sin = self.rope(tokens.device)
         x = self.embed(tokens)
         for i, layer in enumerate(self.layers):
-            x = layer.forward_fp8(x, cos, sin, cache[i], pos)
+            x = layer.forward_fp8(x, cos, sin, cache[i], pos, tiled=tiled)
         if last_only:
             x = x[:, -1:].contiguous()
-        return llm.fp8_linear_q(*llm.rmsnorm_quant_fp8(x, self.norm.weight, self.norm.eps), self._fp8_head)
+        return llm.fp8_linear_q(*llm.rmsnorm_quant_fp8(x, self.norm.weight, self.norm.eps), self._fp8_head,
+                                tiled=tiled)
 
     def decode_fp8_static(self, tok, cache, pos_i32, pos_i64, mask):
         from ..ops import llm
@@ -277,7 +281,8 @@ class LlamaDecoder:
     """Inference tenant: static KV cache, greedy decode."""
 
     def __init__(self, cfg: LlamaConfig, batch: int, context: int, device="cuda", dtype=torch.bfloat16,
-                 fused: Optional[bool] = None, fp8: bool = False, graph: bool = False, static: bool = False):
+                 fused: Optional[bool] = None, fp8: bool = False, graph: bool = False, static: bool = False,
+                 prefill_tiled: bool = False):
         if not 0 < context <= cfg.max_seq:  # the RoPE tables cover max_seq positions
             raise ValueError(f"LlamaDecoder: context {context} must be in [1, max_seq={cfg.max_seq}]")
         self.cfg, self.batch, self.context = cfg, batch, context
@@ -285,6 +290,10 @@ class LlamaDecoder:
         self.model.eval()
         self.fused = (torch.cuda.is_available() and str(device).startswith("cuda")) if fused is None else fused
         self.fp8 = fp8
+        # opt-in: prefill runs the block and head linears on the LDS-tiled fp8
+        # GEMM (one launch per linear) instead of one weight-streaming launch
+        # per 64 rows; decode steps are untouched
+        self.prefill_tiled = prefill_tiled
         if fp8:  # weights streamed as e4m3fn through the fp8 MFMA linears (half the bytes of bf16)
             with torch.no_grad():
                 self.model.attach_fp8()
@@ -303,7 +312,7 @@ class LlamaDecoder:
     def prefill(self, tokens: torch.Tensor) -> torch.Tensor:
         self.pos = 0
         if self.fp8:
-            logits = self.model.forward_fp8(tokens, self.cache, 0, last_only=True)
+            logits = self.model.forward_fp8(tokens, self.cache, 0, last_only=True, tiled=self.prefill_tiled)
         else:
             logits = self.model(tokens, cache=self.cache, pos=0, fused=self.fused, last_only=True)
         self.pos = tokens.shape[1]

@@ -24,7 +24,7 @@ class RunnerStats(C.Structure):
                [("drain_sum_ns", i64), ("drain_max_ns", i64), ("drain_count", u64)]
 
 
-KIND = {"gemm": 1, "stream": 2, "reduce": 3, "gemv": 4, "allreduce": 5}
+KIND = {"gemm": 1, "stream": 2, "reduce": 3, "gemv": 4, "allreduce": 5, "gemm_fp8": 6}
 
 
 def _p(lib, name, res, *args):
@@ -41,6 +41,9 @@ def bind(lib):
     # raw kernels
     _p(lib, "gpbs_hip_gemm_bf16", C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_uint, C.c_uint, vp, vp,
        C.c_int, vp)
+    _p(lib, "gpbs_hip_gemm_fp8", C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_uint,
+       C.c_uint, vp, vp, C.c_int, vp)
+    _p(lib, "gpbs_hip_gemm_fp8_units", C.c_int, C.c_int, C.c_int)
     _p(lib, "gpbs_hip_stream_copy", C.c_int, vp, vp, C.c_ulonglong, C.c_uint, vp, vp, C.c_uint, C.c_uint, vp, vp,
        C.c_int, vp)
     _p(lib, "gpbs_hip_reduce_bf16", C.c_int, vp, vp, vp, C.c_ulonglong, C.c_uint, vp, vp, C.c_uint, C.c_uint, vp, vp,

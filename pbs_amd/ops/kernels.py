@@ -66,6 +66,49 @@ def gemm_bf16(A: torch.Tensor, Bt: torch.Tensor, out: Optional[torch.Tensor] = N
     return out
 
 
+def gemm_fp8_ref(Aq: torch.Tensor, sa: torch.Tensor, Bq: torch.Tensor, sb: torch.Tensor) -> torch.Tensor:
+    """fp32 reference of gemm_fp8 in the kernel's multiplication order:
+    ((Aq @ Bq^T) * sa[m]) * sb[n].  Runs on CPU too."""
+    acc = Aq.float() @ Bq.float().t()
+    return (acc * sa.float().reshape(-1, 1)) * sb.float().reshape(1, -1)
+
+
+def gemm_fp8(Aq: torch.Tensor, sa: torch.Tensor, Bq: torch.Tensor, sb: torch.Tensor,
+             out: Optional[torch.Tensor] = None, *, b_shuffled: bool = False, table=None, tenant: int = 0,
+             counters=None, grid: int = 0, stream=None) -> torch.Tensor:
+    """C[M, N] (bf16) = ((Aq @ Bq^T) * sa[m]) * sb[n] on the block-scaled fp8
+    MFMA (k_gemm_fp8_tn): Aq [M, K], Bq [N, K] e4m3fn, sa [M], sb [N] fp32,
+    fp32 accumulation.  Any M > 0; N % 128 == 0 and K % 128 == 0.
+    ``b_shuffled``: Bq is an ``llm.Fp8Weight.qs`` (lane-order layout, K % 256 == 0)."""
+    f8 = torch.float8_e4m3fn
+    if Aq.dtype != f8 or Bq.dtype != f8 or sa.dtype != torch.float32 or sb.dtype != torch.float32:
+        raise ValueError(f"gemm_fp8 needs e4m3fn operands and fp32 scales, got {Aq.dtype} {Bq.dtype} {sa.dtype} "
+                         f"{sb.dtype}")
+    if Aq.dim() != 2 or Bq.dim() != 2:
+        raise ValueError(f"gemm_fp8 needs 2-D operands, got {tuple(Aq.shape)} x {tuple(Bq.shape)}")
+    M, K = Aq.shape
+    Nn, K2 = Bq.shape
+    if K != K2 or M <= 0 or Nn <= 0 or Nn % 128 or K <= 0 or K % 128:
+        raise ValueError(f"gemm_fp8 needs N % 128 == 0 and K % 128 == 0, got {tuple(Aq.shape)} x {tuple(Bq.shape)}")
+    if b_shuffled and K % 256:
+        raise ValueError(f"gemm_fp8: the shuffled weight layout needs K % 256 == 0, got K={K}")
+    if sa.numel() != M or sb.numel() != Nn:
+        raise ValueError(f"gemm_fp8: scales {tuple(sa.shape)} / {tuple(sb.shape)} for [{M}, {Nn}]")
+    if not (Aq.is_cuda and Bq.is_cuda and sa.is_cuda and sb.is_cuda):
+        raise ValueError("gemm_fp8 needs CUDA tensors")
+    Aq, Bq, sa, sb = Aq.contiguous(), Bq.contiguous(), sa.contiguous(), sb.contiguous()
+    if out is None:
+        out = torch.empty(M, Nn, dtype=torch.bfloat16, device=Aq.device)
+    elif out.dtype != torch.bfloat16 or out.shape != (M, Nn) or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError(f"gemm_fp8: out must be a contiguous bf16 CUDA [{M}, {Nn}], got {out.dtype} {tuple(out.shape)}")
+    q = work_queue(Aq.device)
+    rc = lib().gpbs_hip_gemm_fp8(_ptr(Aq), _ptr(sa), _ptr(Bq), _ptr(sb), _ptr(out), M, Nn, K, int(b_shuffled),
+                                 _ptr(q), table, GATE_TABLE if table else GATE_NONE, tenant, counters, None, grid,
+                                 _stream(stream))
+    _check(rc, "gemm_fp8")
+    return out
+
+
 def stream_copy(src: torch.Tensor, dst: torch.Tensor, *, chunk_bytes: int = 1 << 19, table=None, tenant: int = 0,
                 counters=None, grid: int = 0, stream=None, mode_extra: int = 0):
     """``mode_extra``: gate-mode bits OR-ed in when ``table`` is given

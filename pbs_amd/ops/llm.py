@@ -11,7 +11,7 @@ from typing import Optional
 
 import torch
 
-from .kernels import _check, _ptr, _stream, lib
+from .kernels import _check, _ptr, _stream, gemm_fp8, lib
 
 
 def _need(t: torch.Tensor, what: str):
@@ -180,16 +180,31 @@ class Fp8Weight:
         return self.qs.numel() + 4 * self.s.numel()
 
 
-def fp8_linear_q(xq: torch.Tensor, sx: torch.Tensor, w: Fp8Weight, resid: Optional[torch.Tensor] = None
-                 ) -> torch.Tensor:
+def fp8_shuffled_offset(n: int, k: int, K: int) -> int:
+    """Byte offset in ``Fp8Weight.qs`` of the 16 bytes W[n][k : k + 16]
+    (k % 16 == 0); the Python twin of the staging address of
+    k_gemm_fp8_tn<1> (csrc/hip/fp8_gemm_kernels.hip)."""
+    if k % 16 or K % 256 or not 0 <= k < K:
+        raise ValueError(f"fp8_shuffled_offset: k={k} (k % 16 == 0, 0 <= k < K), K={K} (K % 256 == 0)")
+    return ((n // 16) * (K // 256) + k // 256) * 4096 + ((k % 256) // 64) * 1024 + ((k % 64) // 16) * 256 \
+        + (n % 16) * 16
+
+
+def fp8_linear_q(xq: torch.Tensor, sx: torch.Tensor, w: Fp8Weight, resid: Optional[torch.Tensor] = None,
+                 tiled: bool = False) -> torch.Tensor:
     """y = (xq @ Wq^T) * sx[m] * sw[n] (+ resid, fused into the epilogue) on
     already-quantised rows (the output of quant_rows_fp8 / rmsnorm_quant_fp8 /
-    swiglu_quant_fp8); bf16 out."""
+    swiglu_quant_fp8); bf16 out.  ``tiled`` (opt-in, no resid, N % 128 == 0):
+    one launch of the LDS-tiled fp8 GEMM over the shuffled weight for any M,
+    instead of one weight-streaming launch per 64 rows."""
     lead = xq.shape[:-1]
     if xq.dtype != torch.float8_e4m3fn or xq.shape[-1] != w.K or not xq.is_contiguous():
         raise ValueError(f"fp8_linear_q: need contiguous e4m3fn [..., {w.K}], got {xq.dtype} {tuple(xq.shape)}")
     M = xq.numel() // w.K
     y = torch.empty(*lead, w.N, dtype=torch.bfloat16, device=xq.device)
+    if tiled and resid is None and w.N % 128 == 0:
+        gemm_fp8(xq.view(M, w.K), sx.reshape(M), w.qs, w.s, y.view(M, w.N), b_shuffled=True)
+        return y
     L, st = lib(), _stream()
     if resid is not None:
         _need(resid, "fp8_linear_q resid")
@@ -210,11 +225,12 @@ def fp8_linear_q(xq: torch.Tensor, sx: torch.Tensor, w: Fp8Weight, resid: Option
     return y
 
 
-def fp8_linear(x: torch.Tensor, w: Fp8Weight) -> torch.Tensor:
+def fp8_linear(x: torch.Tensor, w: Fp8Weight, tiled: bool = False) -> torch.Tensor:
     """y = x @ W^T with W in fp8 and x quantised per token to fp8 on the fly;
-    fp32 MFMA accumulation, bf16 output.  x [..., K] bf16."""
+    fp32 MFMA accumulation, bf16 output.  x [..., K] bf16.  ``tiled``: as
+    fp8_linear_q."""
     xq, sx = quant_rows_fp8(x)
-    return fp8_linear_q(xq, sx, w)
+    return fp8_linear_q(xq, sx, w, tiled=tiled)
 
 
 def rmsnorm_quant_fp8(x: torch.Tensor, w: torch.Tensor, eps: float):

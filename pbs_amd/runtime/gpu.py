@@ -414,7 +414,7 @@ class RunnerStats:
 
 
 class Runner:
-    """Native tenant worker.  ``kind`` in {gemm, stream, reduce, gemv}.
+    """Native tenant worker.  ``kind`` in {gemm, gemm_fp8, stream, reduce, gemv, allreduce}.
 
     ``alt`` (optional): a second workload ``dict(kind=..., **shape)`` for a
     phase-changing tenant; ``set_phase(1)`` makes every fresh unit run it
@@ -467,6 +467,26 @@ class Runner:
             b = torch.randn(Nn, K, device=dev, dtype=torch.bfloat16, generator=g)
             c = torch.empty(M, Nn, device=dev, dtype=torch.bfloat16)
             work, unit = 2.0 * M * Nn * K, "FLOP"
+        elif kind == "gemm_fp8":
+            # e4m3 rows (randn through quant_rows_fp8) followed by their fp32
+            # scales in ONE allocation per operand: the native runner derives
+            # the scale pointers from M, N, K (K % 128 keeps them aligned)
+            from ..ops import llm
+            M, Nn, K = shape.get("M", 4096), shape.get("N", 4096), shape.get("K", 4096)
+            if M % 128 or Nn % 128 or K % 128 or min(M, Nn, K) <= 0:
+                raise ValueError(f"gemm_fp8 runner needs M, N, K % 128 == 0, got {M} x {Nn} x {K}")
+            packed = []
+            for rows in (M, Nn):
+                with torch.cuda.device(dev):  # the quantiser launches on the current device's stream
+                    q, s = llm.quant_rows_fp8(torch.randn(rows, K, device=dev, dtype=torch.bfloat16, generator=g))
+                p = torch.empty(rows * K + 4 * rows, device=dev, dtype=torch.uint8)
+                p[:rows * K].copy_(q.view(torch.uint8).reshape(-1))
+                p[rows * K:].view(torch.float32).copy_(s)
+                packed.append(p)
+            a, b = packed
+            c = torch.empty(M, Nn, device=dev, dtype=torch.bfloat16)
+            self._fp8 = (M, Nn, K, a, b, c)
+            work, unit = 2.0 * M * Nn * K, "FLOP"
         elif kind in ("stream", "reduce"):
             nbytes = int(shape.get("bytes", 1 << 30))
             chunk = int(shape.get("chunk_bytes", 1 << 19))
@@ -497,6 +517,17 @@ class Runner:
         return {"kind": hipabi.KIND[kind], "M": M, "N": Nn, "K": K, "chunk": chunk, "bytes": nbytes,
                 "a": a.data_ptr(), "b": b.data_ptr() if b is not None else None, "c": c.data_ptr(),
                 "work": work, "unit": unit}
+
+    def fp8_operands(self):
+        """``(Aq, sa, Bq, sb, C)`` views of a gemm_fp8 workload's packed
+        buffers (the last one built: the alternate workload if it is the
+        gemm_fp8 one)."""
+        if getattr(self, "_fp8", None) is None:
+            raise ValueError(f"runner {self.kind} has no gemm_fp8 workload")
+        M, Nn, K, a, b, c = self._fp8
+        f8 = torch.float8_e4m3fn
+        return (a[:M * K].view(f8).view(M, K), a[M * K:].view(torch.float32),
+                b[:Nn * K].view(f8).view(Nn, K), b[Nn * K:].view(torch.float32), c)
 
     def set_phase(self, alt: int) -> int:
         """Phase-changing tenant: fresh units run the alternate workload (1)

@@ -1,8 +1,12 @@
 """fp8 decode microbench (config #5): the gfx950 fp8 MFMA linear against the
 bf16 hipBLASLt product (torch.matmul) on the Llama-3-8B decode shapes, then a
-whole llama3-8b decode step (batch 8) on bf16 vs fp8 weights.
+whole llama3-8b decode step (batch 8) on bf16 vs fp8 weights.  The prefill
+rows time fp8_linear_q on M = 512 and 2048 rows (N = K = 4096) tiled (one
+launch of the LDS-tiled fp8 GEMM) against sliced (one weight-streaming launch
+per 64 rows): profiles/fp8_prefill_tiled.jsonl.
 
     python scripts/fp8_bench.py [--batch 8] [--iters 50] [--out gpurun_out/fp8_bench.jsonl]
+    python scripts/fp8_bench.py --prefill-only --out FILE     # only the prefill rows
 """
 import argparse
 import json
@@ -39,7 +43,10 @@ def main():
     ap.add_argument("--skip-linear", action="store_true")
     ap.add_argument("--variants", default="bf16,fp8,fp8+graph")
     ap.add_argument("--out", default="")
+    ap.add_argument("--prefill-only", action="store_true", help="only the tiled vs sliced prefill linear rows")
     a = ap.parse_args()
+    if a.prefill_only:
+        a.skip_linear = a.skip_model = True
     out = open(a.out, "a") if a.out else None
 
     def emit(rec):
@@ -76,6 +83,25 @@ def main():
               "bf16_TBps": round(N * K * 2 / t16 / 1e6, 3), "fp8_kernel_TBps": round(N * K / tk / 1e6, 3),
               "speedup": round(t16 / t8, 3)})
         del w, W, x
+    # prefill linear: tiled vs sliced on the same quantised rows, alternating
+    # rounds in one process; median of the rounds
+    for M in (512, 2048):
+        N = K = 4096
+        W = llm.Fp8Weight((torch.randn(N, K, device="cuda", generator=g) * 0.02).bfloat16())
+        xq, sx = llm.quant_rows_fp8(torch.randn(M, K, device="cuda", generator=g).bfloat16())
+        ts, tt = [], []
+        for _ in range(5):
+            ts.append(timeit(lambda: llm.fp8_linear_q(xq, sx, W), a.iters))
+            tt.append(timeit(lambda: llm.fp8_linear_q(xq, sx, W, tiled=True), a.iters))
+        sliced, tiled = sorted(ts)[2], sorted(tt)[2]
+        ys, yt = llm.fp8_linear_q(xq, sx, W).float(), llm.fp8_linear_q(xq, sx, W, tiled=True).float()
+        emit({"bench": "prefill_linear", "M": M, "N": N, "K": K, "sliced_us": round(sliced, 2),
+              "tiled_us": round(tiled, 2), "speedup_tiled_vs_sliced": round(sliced / tiled, 3),
+              "sliced_TFs": round(2.0 * M * N * K / sliced / 1e6, 1), "tiled_TFs": round(2.0 * M * N * K / tiled / 1e6, 1),
+              "sliced_us_minmax": [round(min(ts), 2), round(max(ts), 2)],
+              "tiled_us_minmax": [round(min(tt), 2), round(max(tt), 2)],
+              "max_abs_diff": (ys - yt).abs().max().item(), "max_abs": ys.abs().max().item()})
+        del W, xq, sx
     torch.cuda.empty_cache()
     if a.skip_model:
         return

@@ -3,9 +3,11 @@
 Reports GEMM TF/s (bf16 MFMA, fp32 acc), stream-copy and reduce-copy TB/s
 (bytes read + written) across launch grids, each against the PyTorch/hipBLASLt
 equivalent, as one JSON line per measurement.  Used to size the default grids
-(see SUNROLL in csrc/hip/tenant_kernels.hip).
+(see SUNROLL in csrc/hip/tenant_kernels.hip).  The fp8 (e4m3) GEMM rows
+compare it with the bf16 128-tile kernel on the same shape and with the
+shipped 256-tile bf16 GEMM (profiles/kbench_gemm_fp8.jsonl).
 
-    python scripts/kbench.py [--iters 20]
+    python scripts/kbench.py [--iters 20] [--gemm-fp8]
 """
 from __future__ import annotations
 
@@ -41,9 +43,62 @@ def timed(fn, iters, pre=None):
     return ts[len(ts) // 2]
 
 
+def gemm_fp8_rows(L, s, q, iters, rounds=5):
+    """fp8 (e4m3) 128-tile GEMM against two bf16 baselines, interleaved rounds
+    in one process: (a) the bf16 128-tile kernel on the same shape (4224 is no
+    multiple of 256, so gemm_bf16 takes its 128-tile path), (b) the shipped
+    256-tile bf16 GEMM at 4096^3.  randn operands (rows through quant_rows_fp8
+    for the fp8 arms); median of `rounds` medians of `iters` launches."""
+    from pbs_amd.ops import llm
+    dev, zero = "cuda", q.zero_
+    g = torch.Generator(device=dev).manual_seed(0)
+    arms, bufs = {}, {}
+    for m, n, k in ((4224, 4224, 4096), (4096, 4096, 4096)):
+        a = torch.randn(m, k, device=dev, dtype=torch.bfloat16, generator=g)
+        b = torch.randn(n, k, device=dev, dtype=torch.bfloat16, generator=g)
+        c = torch.empty(m, n, device=dev, dtype=torch.bfloat16)
+        aq, sa = llm.quant_rows_fp8(a)
+        w = llm.Fp8Weight(b)  # shuffled copy; w.q is the row-major one
+        bq = w.q
+        bufs[(m, n, k)] = (a, b, c, aq, sa, bq, w)
+        arms[("gemm_bf16", "128-tile" if m % 256 else "256-tile-shipped", m, n, k)] = (
+            lambda a=a, b=b, c=c, m=m, n=n, k=k: L.gpbs_hip_gemm_bf16(K._ptr(a), K._ptr(b), K._ptr(c), m, n, k,
+                                                                     K._ptr(q), None, 0, 0, None, None, 0, s))
+        for shuf in (0, 1):
+            arms[("gemm_fp8", "b-shuffled" if shuf else "row-major", m, n, k)] = (
+                lambda aq=aq, sa=sa, bp=(w.qs if shuf else bq), sb=w.s, c=c, m=m, n=n, k=k, shuf=shuf:
+                L.gpbs_hip_gemm_fp8(K._ptr(aq), K._ptr(sa), K._ptr(bp), K._ptr(sb), K._ptr(c), m, n, k, shuf,
+                                    K._ptr(q), None, 0, 0, None, None, 0, s))
+    ts = {key: [] for key in arms}
+    for _ in range(rounds):
+        for key, fn in arms.items():
+            ts[key].append(timed(fn, iters, zero))
+    out, tf = [], {}
+    for (kern, var, m, n, k), v in ts.items():
+        ms = sorted(v)[len(v) // 2]
+        tf[(kern, var, m)] = 2.0 * m * n * k / ms / 1e9
+        out.append({"kernel": kern, "variant": var, "shape": [m, n, k], "ms": ms, "tflops": tf[(kern, var, m)],
+                    "min_ms": min(v), "max_ms": max(v)})
+    out.append({"kernel": "gemm_fp8", "ratio": "fp8 row-major 4224x4224x4096 / bf16 128-tile same shape",
+                "value": tf[("gemm_fp8", "row-major", 4224)] / tf[("gemm_bf16", "128-tile", 4224)]})
+    out.append({"kernel": "gemm_fp8", "ratio": "fp8 row-major 4096^3 / bf16 256-tile shipped 4096^3",
+                "value": tf[("gemm_fp8", "row-major", 4096)] / tf[("gemm_bf16", "256-tile-shipped", 4096)]})
+    # results: both fp8 arms against the fp32 product of the same operands (a slice)
+    for (m, n, k), (a, b, c, aq, sa, bq, w) in bufs.items():
+        ref = K.gemm_fp8_ref(aq[:512], sa[:512], bq, w.s)
+        for shuf in (0, 1):
+            zero()
+            y = K.gemm_fp8(aq, sa, w.qs if shuf else bq, w.s, b_shuffled=bool(shuf))
+            err = (y[:512].float() - ref).abs().max().item()
+            out.append({"kernel": "gemm_fp8", "variant": "b-shuffled" if shuf else "row-major", "shape": [m, n, k],
+                        "check_max_abs_err": err, "ok": err <= 1e-2 * ref.abs().max().item()})
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--gemm-fp8", action="store_true", help="only the fp8 GEMM rows and their bf16 baselines")
     args = ap.parse_args()
     L = K.lib()
     s = K._stream()
@@ -51,6 +106,10 @@ def main():
     zero = q.zero_
     dev = "cuda"
     out = []
+    if args.gemm_fp8:
+        for r in gemm_fp8_rows(L, s, q, args.iters):
+            print(json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in r.items()}))
+        return
     n = 4096 if not os.environ.get("KBENCH_NO_GEMM") else 256  # KBENCH_NO_GEMM: streams / reduce only
     A = torch.randn(n, n, device=dev, dtype=torch.bfloat16)
     B = torch.randn(n, n, device=dev, dtype=torch.bfloat16)
@@ -100,6 +159,9 @@ def main():
         for r in out:
             print(json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in r.items()}))
         return
+
+    if not os.environ.get("KBENCH_NO_GEMM"):
+        out += gemm_fp8_rows(L, s, q, args.iters)
 
     nbytes = 1 << 30
     src = torch.empty(nbytes // 4, device=dev, dtype=torch.float32).normal_()
