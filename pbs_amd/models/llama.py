@@ -98,7 +98,7 @@ class Block(nn.Module):
         self.w3 = nn.Linear(cfg.dim, cfg.ffn_dim, bias=False)  # up
         self.w2 = nn.Linear(cfg.ffn_dim, cfg.dim, bias=False)  # down
 
-    def attention(self, h, cos, sin, cache=None, pos: int = 0, fused: bool = False):
+    def attention(self, h, cos, sin, cache=None, pos: int = 0, fused: bool = False, prefill_attn: bool = False):
         B, S, _ = h.shape
         cfg, hd = self.cfg, self.cfg.head_dim
         q = self.wq(h).view(B, S, cfg.n_heads, hd)
@@ -114,6 +114,11 @@ class Block(nn.Module):
             kc, vc = cache
             kc[:, :, pos:pos + S] = k.transpose(1, 2)
             vc[:, :, pos:pos + S] = v.transpose(1, 2)
+            if prefill_attn and S > 1:  # causal mask offset by pos: correct for any chunk of a prompt
+                from ..ops import llm
+                if fused:
+                    return self.wo(llm.prefill_attn(q, kc, vc, pos))
+                return self.wo(llm.prefill_attn_ref(q, kc, vc, pos).to(h.dtype))
             k_all, v_all = kc[:, :, :pos + S], vc[:, :, :pos + S]
         else:
             k_all, v_all = k.transpose(1, 2), v.transpose(1, 2)
@@ -134,26 +139,34 @@ class Block(nn.Module):
             "w2": llm.Fp8Weight(self.w2.weight),
         }
 
-    def forward_fp8(self, x, cos, sin, cache, pos: int, tiled: bool = False):
+    def forward_fp8(self, x, cos, sin, cache, pos: int, tiled: bool = False, prefill_attn: bool = False):
         """Decode/prefill block on fp8 weights (fp8 MFMA linears + fused gfx950
         RMSNorm/RoPE/SwiGLU); inference only.  ``tiled``: the linears run the
-        LDS-tiled fp8 GEMM (one launch for any M) where their N allows it."""
+        LDS-tiled fp8 GEMM (one launch for any M) where their N allows it.
+        ``prefill_attn``: for S > 1 the attention block is two gfx950 launches
+        (qkv_rope_cache_prefill, prefill_attn) instead of RoPE, cache copies and
+        SDPA."""
         from ..ops import llm
         cfg, hd, f = self.cfg, self.cfg.head_dim, self._fp8
         B, S, _ = x.shape
         qkv = llm.fp8_linear_q(*llm.rmsnorm_quant_fp8(x, self.attn_norm.weight, self.attn_norm.eps), f["qkv"],
                                tiled=tiled)
         nq, nkv = cfg.n_heads * hd, cfg.n_kv_heads * hd
-        q = qkv[..., :nq].reshape(B, S, cfg.n_heads, hd)
-        k = qkv[..., nq:nq + nkv].reshape(B, S, cfg.n_kv_heads, hd)
-        v = qkv[..., nq + nkv:].reshape(B, S, cfg.n_kv_heads, hd)
-        q, k = llm.rope(q, cos, sin, pos), llm.rope(k, cos, sin, pos)
         kc, vc = cache
-        kc[:, :, pos:pos + S] = k.transpose(1, 2)
-        vc[:, :, pos:pos + S] = v.transpose(1, 2)
-        o = F.scaled_dot_product_attention(q.transpose(1, 2), kc[:, :, :pos + S], vc[:, :, :pos + S],
-                                           is_causal=(S > 1), enable_gqa=True)
-        x = x + llm.fp8_linear(o.transpose(1, 2).reshape(B, S, nq), f["o"], tiled=tiled)
+        if prefill_attn and S > 1:
+            q = llm.qkv_rope_cache_prefill(qkv, cos, sin, pos, kc, vc, cfg.n_heads)
+            o = llm.prefill_attn(q, kc, vc, pos)
+        else:
+            q = qkv[..., :nq].reshape(B, S, cfg.n_heads, hd)
+            k = qkv[..., nq:nq + nkv].reshape(B, S, cfg.n_kv_heads, hd)
+            v = qkv[..., nq + nkv:].reshape(B, S, cfg.n_kv_heads, hd)
+            q, k = llm.rope(q, cos, sin, pos), llm.rope(k, cos, sin, pos)
+            kc[:, :, pos:pos + S] = k.transpose(1, 2)
+            vc[:, :, pos:pos + S] = v.transpose(1, 2)
+            o = F.scaled_dot_product_attention(q.transpose(1, 2), kc[:, :, :pos + S], vc[:, :, :pos + S],
+                                               is_causal=(S > 1), enable_gqa=True)
+            o = o.transpose(1, 2).reshape(B, S, nq)
+        x = x + llm.fp8_linear(o, f["o"], tiled=tiled)
         gu = llm.fp8_linear_q(*llm.rmsnorm_quant_fp8(x, self.mlp_norm.weight, self.mlp_norm.eps), f["w13"],
                               tiled=tiled)
         return x + llm.fp8_linear_q(*llm.swiglu_quant_fp8(gu), f["w2"], tiled=tiled)
@@ -188,14 +201,14 @@ class Block(nn.Module):
         gu = llm.fp8_linear_q(*llm.rmsnorm_quant_fp8(x, self.mlp_norm.weight, self.mlp_norm.eps), f["w13"])
         return x + llm.fp8_linear_q(*llm.swiglu_quant_fp8(gu), f["w2"])
 
-    def forward(self, x, cos, sin, cache=None, pos: int = 0, fused: bool = False):
+    def forward(self, x, cos, sin, cache=None, pos: int = 0, fused: bool = False, prefill_attn: bool = False):
         if fused:
             from ..ops import llm
             h = llm.rmsnorm(x, self.attn_norm.weight, self.attn_norm.eps)
-            x = x + self.attention(h, cos, sin, cache, pos, fused=True)
+            x = x + self.attention(h, cos, sin, cache, pos, fused=True, prefill_attn=prefill_attn)
             h = llm.rmsnorm(x, self.mlp_norm.weight, self.mlp_norm.eps)
             return x + self.w2(llm.swiglu(self.w1(h), self.w3(h)))
-        x = x + self.attention(self.attn_norm(x), cos, sin, cache, pos)
+        x = x + self.attention(self.attn_norm(x), cos, sin, cache, pos, prefill_attn=prefill_attn)
         h = self.mlp_norm(x)
         return x + self.w2(F.silu(self.w1(h)) * self.w3(h))
 
@@ -233,12 +246,17 @@ class Llama(nn.Module):
         self._fp8_head = llm.Fp8Weight(self.lm_head.weight)
         return self
 
-    def forward_fp8(self, tokens, cache, pos: int = 0, last_only: bool = False, tiled: bool = False):
+    def forward_fp8(self, tokens, cache, pos: int = 0, last_only: bool = False, tiled: bool = False,
+                    prefill_attn: bool = False, head: bool = True):
+        """``head=False`` (a non-final chunk of a chunked prefill): fill the
+        caches only, no final norm / LM head; returns None."""
         from ..ops import llm
         cos, sin = self.rope(tokens.device)
         x = self.embed(tokens)
         for i, layer in enumerate(self.layers):
-            x = layer.forward_fp8(x, cos, sin, cache[i], pos, tiled=tiled)
+            x = layer.forward_fp8(x, cos, sin, cache[i], pos, tiled=tiled, prefill_attn=prefill_attn)
+        if not head:
+            return None
         if last_only:
             x = x[:, -1:].contiguous()
         return llm.fp8_linear_q(*llm.rmsnorm_quant_fp8(x, self.norm.weight, self.norm.eps), self._fp8_head,
@@ -252,11 +270,14 @@ class Llama(nn.Module):
             x = layer.decode_fp8_static(x, cos, sin, cache[i], pos_i32, pos_i64, mask)
         return llm.fp8_linear_q(*llm.rmsnorm_quant_fp8(x, self.norm.weight, self.norm.eps), self._fp8_head)
 
-    def forward(self, tokens, cache=None, pos: int = 0, fused: bool = False, last_only: bool = False):
+    def forward(self, tokens, cache=None, pos: int = 0, fused: bool = False, last_only: bool = False,
+                prefill_attn: bool = False, head: bool = True):
         cos, sin = self.rope(tokens.device)
         x = self.embed(tokens)
         for i, layer in enumerate(self.layers):
-            x = layer(x, cos, sin, None if cache is None else cache[i], pos, fused)
+            x = layer(x, cos, sin, None if cache is None else cache[i], pos, fused, prefill_attn)
+        if not head:  # a non-final chunk of a chunked prefill: the caches are filled, no logits
+            return None
         if last_only:
             x = x[:, -1:]
         x = self.norm(x) if not fused else __import__("pbs_amd.ops.llm", fromlist=["rmsnorm"]).rmsnorm(
@@ -282,7 +303,7 @@ class LlamaDecoder:
 
     def __init__(self, cfg: LlamaConfig, batch: int, context: int, device="cuda", dtype=torch.bfloat16,
                  fused: Optional[bool] = None, fp8: bool = False, graph: bool = False, static: bool = False,
-                 prefill_tiled: bool = False):
+                 prefill_tiled: bool = False, prefill_attn: bool = False):
         if not 0 < context <= cfg.max_seq:  # the RoPE tables cover max_seq positions
             raise ValueError(f"LlamaDecoder: context {context} must be in [1, max_seq={cfg.max_seq}]")
         self.cfg, self.batch, self.context = cfg, batch, context
@@ -294,6 +315,15 @@ class LlamaDecoder:
         # GEMM (one launch per linear) instead of one weight-streaming launch
         # per 64 rows; decode steps are untouched
         self.prefill_tiled = prefill_tiled
+        # opt-in: calls with S > 1 run causal GQA attention offset by the cache
+        # position (the gfx950 MFMA kernel on the fused / fp8 paths, its torch
+        # reference on the eager path), which is what lets a prompt be prefilled
+        # in chunks; S == 1 steps and the static / graph decode are untouched
+        G = cfg.n_heads // cfg.n_kv_heads
+        if prefill_attn and (cfg.head_dim != 128 or cfg.n_heads % cfg.n_kv_heads or G not in (1, 2, 4, 8)):
+            raise ValueError(f"LlamaDecoder: prefill_attn needs head_dim 128 and n_heads / n_kv_heads in 1/2/4/8, "
+                             f"got head_dim {cfg.head_dim}, {cfg.n_heads} / {cfg.n_kv_heads} heads")
+        self.prefill_attn = prefill_attn
         if fp8:  # weights streamed as e4m3fn through the fp8 MFMA linears (half the bytes of bf16)
             with torch.no_grad():
                 self.model.attach_fp8()
@@ -308,14 +338,55 @@ class LlamaDecoder:
                       for _ in range(cfg.n_layers)]
         self.pos = 0
 
-    @torch.no_grad()
-    def prefill(self, tokens: torch.Tensor) -> torch.Tensor:
-        self.pos = 0
+    def _forward(self, tokens, pos: int, head: bool = True):
         if self.fp8:
-            logits = self.model.forward_fp8(tokens, self.cache, 0, last_only=True, tiled=self.prefill_tiled)
-        else:
-            logits = self.model(tokens, cache=self.cache, pos=0, fused=self.fused, last_only=True)
+            return self.model.forward_fp8(tokens, self.cache, pos, last_only=True, tiled=self.prefill_tiled,
+                                          prefill_attn=self.prefill_attn, head=head)
+        return self.model(tokens, cache=self.cache, pos=pos, fused=self.fused, last_only=True,
+                          prefill_attn=self.prefill_attn, head=head)
+
+    @torch.no_grad()
+    def prefill(self, tokens: torch.Tensor, chunk: Optional[int] = None) -> torch.Tensor:
+        """Run the prompt into the KV cache and return the next token [B, 1].
+        ``chunk``: run it in pieces of at most that many tokens (prefill_iter,
+        drained here); needs prefill_attn=True."""
+        if chunk is not None:
+            it = self.prefill_iter(tokens, chunk)
+            while True:
+                try:
+                    next(it)
+                except StopIteration as e:
+                    return e.value
+        self.pos = 0
+        logits = self._forward(tokens, 0)
         self.pos = tokens.shape[1]
+        return logits[:, -1].argmax(-1, keepdim=True)
+
+    def prefill_iter(self, tokens: torch.Tensor, chunk: int):
+        """Chunked prefill as a generator: runs tokens[:, c : c + chunk] at cache
+        position c = 0, chunk, 2 chunk, ... and yields the number of prompt
+        tokens done after each chunk, so a scheduled tenant can give every
+        chunk a slice of its own.  Only the last chunk computes logits; the next
+        token [B, 1] is the generator's return value (StopIteration.value)."""
+        if not self.prefill_attn:
+            raise ValueError("LlamaDecoder: chunked prefill needs prefill_attn=True (SDPA's is_causal mask is "
+                             "top-left aligned, wrong for a chunk at pos > 0)")
+        if not isinstance(chunk, int) or isinstance(chunk, bool) or chunk < 1:
+            raise ValueError(f"LlamaDecoder: chunk must be a positive int, got {chunk!r}")
+        S = tokens.shape[1]
+        if not 0 < S <= self.context:
+            raise ValueError(f"LlamaDecoder: prompt of {S} tokens for a context of {self.context}")
+        return self._prefill_chunks(tokens, chunk)
+
+    def _prefill_chunks(self, tokens: torch.Tensor, chunk: int):
+        S = tokens.shape[1]
+        self.pos, logits = 0, None
+        for c0 in range(0, S, chunk):
+            c1 = min(S, c0 + chunk)
+            with torch.no_grad():
+                logits = self._forward(tokens[:, c0:c1], c0, head=(c1 == S))
+            self.pos = c1
+            yield c1
         return logits[:, -1].argmax(-1, keepdim=True)
 
     def _graph_setup(self, tok: torch.Tensor):

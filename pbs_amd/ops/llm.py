@@ -121,6 +121,102 @@ def decode_attn(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, pos_t: torc
                                       Hkv, Cn, hd, C.c_float(hd ** -0.5), _stream()), "decode_attn")
     return out
 
+
+# --------------------------------------------------------------------------- prefill (csrc/hip/prefill_kernels.hip)
+def _prefill_geom(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, pos: int, what: str):
+    """Shape contract of k_prefill_attn, checked on the host tensors alone."""
+    if q.dim() != 4 or kc.dim() != 4 or vc.shape != kc.shape:
+        raise ValueError(f"{what}: q {tuple(q.shape)} must be [B, S, H, hd], caches {tuple(kc.shape)} / "
+                         f"{tuple(vc.shape)} [B, Hkv, C, hd]")
+    B, S, H, hd = q.shape
+    Bc, Hkv, Cn, hdc = kc.shape
+    if hd != 128 or hdc != 128:
+        raise ValueError(f"{what}: head_dim 128 required, got q {hd} / cache {hdc}")
+    if Bc != B or S < 1 or Hkv < 1 or H % Hkv or (H // Hkv) not in (1, 2, 4, 8):
+        raise ValueError(f"{what}: q {tuple(q.shape)} vs cache {tuple(kc.shape)} (same batch, group size "
+                         f"H / Hkv in 1/2/4/8)")
+    if not isinstance(pos, int) or isinstance(pos, bool) or pos < 0 or pos + S > Cn:
+        raise ValueError(f"{what}: pos={pos!r} with S={S} must satisfy 0 <= pos and pos + S <= C={Cn}")
+    for name, t in (("q", q), ("kc", kc), ("vc", vc)):
+        if t.dtype != torch.bfloat16:
+            raise ValueError(f"{what}: {name} must be bf16, got {t.dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be contiguous (strides {t.stride()})")
+    return B, S, H, Hkv, Cn, hd
+
+
+def prefill_attn(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, pos: int) -> torch.Tensor:
+    """Causal grouped-query attention of S new tokens over the static KV cache
+    (k_prefill_attn, bf16 MFMA): q [B, S, H, 128] (RoPE applied), caches
+    [B, Hkv, C, 128] already holding rows pos .. pos + S - 1; query s attends
+    cache rows 0 .. pos + s.  Returns [B, S, H * 128] bf16.  Rows >= pos + S of
+    the caches are never read."""
+    B, S, H, Hkv, Cn, hd = _prefill_geom(q, kc, vc, pos, "prefill_attn")
+    _need(q, "prefill_attn q")
+    _need(kc, "prefill_attn kc")
+    _need(vc, "prefill_attn vc")
+    out = torch.empty(B, S, H * hd, dtype=torch.bfloat16, device=q.device)
+    _check(lib().gpbs_hip_prefill_attn(_ptr(q), _ptr(kc), _ptr(vc), _ptr(out), B, S, H, Hkv, Cn, hd, pos,
+                                       C.c_float(hd ** -0.5), _stream()), "prefill_attn")
+    return out
+
+
+def prefill_attn_ref(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, pos: int) -> torch.Tensor:
+    """Plain-torch reference of prefill_attn for any head_dim / group size (runs
+    on CPU too): fp32 compute, fp64 for fp64 inputs, grouped per KV head without
+    repeating K/V, mask key <= pos + s.  Returns [B, S, H * hd] in the compute
+    dtype."""
+    B, S, H, hd = q.shape
+    Hkv, Cn = kc.shape[1], kc.shape[2]
+    if kc.shape[0] != B or kc.shape[3] != hd or vc.shape != kc.shape or H % Hkv or pos < 0 or pos + S > Cn:
+        raise ValueError(f"prefill_attn_ref: q {tuple(q.shape)}, cache {tuple(kc.shape)}, pos={pos}")
+    ct = torch.float64 if q.dtype == torch.float64 else torch.float32
+    L, G = pos + S, H // Hkv
+    qg = q.to(ct).view(B, S, Hkv, G, hd).permute(0, 2, 3, 1, 4)  # [B, Hkv, G, S, hd]
+    k, v = kc[:, :, :L].to(ct), vc[:, :, :L].to(ct)
+    sc = torch.matmul(qg, k.transpose(-1, -2).unsqueeze(2)) * (hd ** -0.5)  # [B, Hkv, G, S, L]
+    seen = torch.arange(L, device=q.device)[None, :] <= pos + torch.arange(S, device=q.device)[:, None]
+    sc = sc.masked_fill(~seen, float("-inf"))
+    o = torch.matmul(torch.softmax(sc, -1), v.unsqueeze(2))  # [B, Hkv, G, S, hd]
+    return o.permute(0, 3, 1, 2, 4).reshape(B, S, H * hd)
+
+
+def qkv_rope_cache_prefill(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: int, kc: torch.Tensor,
+                           vc: torch.Tensor, n_heads: int) -> torch.Tensor:
+    """S-token form of qkv_rope_cache with a host position: split the packed qkv
+    [B, S, (H + 2 Hkv) hd], RoPE q and k at angle rows pos + s, write k / v into
+    rows pos .. pos + S - 1 of the caches [B, Hkv, C, hd]; returns q [B, S, H, hd]."""
+    if qkv.dim() != 3 or kc.dim() != 4 or vc.shape != kc.shape:
+        raise ValueError(f"qkv_rope_cache_prefill: qkv {tuple(qkv.shape)} must be [B, S, (H + 2 Hkv) hd], caches "
+                         f"{tuple(kc.shape)} / {tuple(vc.shape)}")
+    B, Hkv, Cn, hd = kc.shape
+    S = qkv.shape[1]
+    if qkv.shape[0] != B or S < 1 or qkv.shape[2] != (n_heads + 2 * Hkv) * hd or hd % 8 or cos.dim() != 2 \
+            or cos.shape[-1] * 2 != hd:
+        raise ValueError(f"qkv_rope_cache_prefill: qkv {tuple(qkv.shape)} vs cache {tuple(kc.shape)}, H={n_heads}, "
+                         f"rope tables {tuple(cos.shape)}")
+    if not isinstance(pos, int) or isinstance(pos, bool) or pos < 0 or pos + S > Cn:
+        raise ValueError(f"qkv_rope_cache_prefill: pos={pos!r} with S={S} must satisfy 0 <= pos and "
+                         f"pos + S <= C={Cn}")
+    if cos.shape[0] < pos + S or sin.shape != cos.shape or cos.dtype != torch.float32 or sin.dtype != torch.float32 \
+            or not (cos.is_contiguous() and sin.is_contiguous()):
+        raise ValueError(f"qkv_rope_cache_prefill: rope tables {tuple(cos.shape)} {cos.dtype} must be contiguous "
+                         f"fp32 and cover pos + S = {pos + S} rows")
+    for name, t in (("qkv", qkv), ("kc", kc), ("vc", vc)):
+        if t.dtype != torch.bfloat16 or not t.is_contiguous():
+            raise ValueError(f"qkv_rope_cache_prefill: {name} must be contiguous bf16, got {t.dtype} strides "
+                             f"{t.stride()}")
+    _need(qkv, "qkv_rope_cache_prefill qkv")
+    _need(kc, "qkv_rope_cache_prefill kc")
+    _need(vc, "qkv_rope_cache_prefill vc")
+    if not (cos.is_cuda and sin.is_cuda):
+        raise ValueError("qkv_rope_cache_prefill: rope tables must be CUDA tensors")
+    q = torch.empty(B, S, n_heads, hd, dtype=torch.bfloat16, device=qkv.device)
+    _check(lib().gpbs_hip_qkv_rope_cache_prefill(_ptr(qkv), _ptr(cos), _ptr(sin), _ptr(q), _ptr(kc), _ptr(vc), B, S,
+                                                 n_heads, Hkv, Cn, hd, pos, _stream()), "qkv_rope_cache_prefill")
+    return q
+
+
 # --------------------------------------------------------------------------- fp8 (config #5, CDNA4 fp8 MFMA)
 FP8_MAX = 448.0  # OCP e4m3fn (gfx950), not the MI300 fnuz variant
 FP8_M_TILE = 64  # rows per gpbs_hip_fp8_linear launch

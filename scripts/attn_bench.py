@@ -1,0 +1,179 @@
+"""Prefill attention microbench: the gfx950 MFMA kernel (llm.prefill_attn)
+against F.scaled_dot_product_attention(enable_gqa=True) on the same tensors,
+with the transposes SDPA needs counted (the model pays for them), on the
+Llama-3-8B head geometry (H 32, Hkv 8, head_dim 128); then a whole llama3-8b fp8
+prefill (batch 8, 1024-token prompt) with and without prefill_attn, unchunked
+and in chunks of 256 (and the same on the bf16 weights), with the cosine of the
+last-token logits against the SDPA run.  Rounds alternate the variants in one process; a row
+reports the median of 5 rounds with min / max.
+
+    python scripts/attn_bench.py [--iters 100] [--out prefill_attn.jsonl] [--skip-model]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from pbs_amd.models.llama import PRESETS, LlamaDecoder  # noqa: E402
+from pbs_amd.ops import llm  # noqa: E402
+
+H, HKV, HD = 32, 8, 128
+ROUNDS = 5
+
+
+def timeit(fn, iters):
+    for _ in range(2):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters * 1e3  # us
+
+
+def med(ts):
+    return sorted(ts)[len(ts) // 2]
+
+
+def flops(B, S, pos):
+    return 4.0 * B * H * HD * S * (pos + (S + 1) / 2)
+
+
+def kernel_row(emit, g, iters, B, S, pos, C, name, sdpa=True):
+    q = torch.randn(B, S, H, HD, device="cuda", generator=g).bfloat16()
+    kc = torch.randn(B, HKV, C, HD, device="cuda", generator=g).bfloat16()
+    vc = torch.randn(B, HKV, C, HD, device="cuda", generator=g).bfloat16()
+    L = pos + S
+    # is_causal is top-left aligned: only right for pos == 0; a chunk needs the explicit mask
+    mask = None if pos == 0 else \
+        (torch.arange(L, device="cuda")[None, :] <= pos + torch.arange(S, device="cuda")[:, None])
+
+    def ours():
+        return llm.prefill_attn(q, kc, vc, pos)
+
+    def theirs():
+        o = F.scaled_dot_product_attention(q.transpose(1, 2), kc[:, :, :L], vc[:, :, :L], attn_mask=mask,
+                                           is_causal=mask is None, enable_gqa=True)
+        return o.transpose(1, 2).reshape(B, S, H * HD)
+
+    err = None
+    if sdpa:
+        try:
+            theirs()
+        except Exception as e:  # recorded in the row: the comparison is then missing, not the kernel's time
+            sdpa, err = False, f"{type(e).__name__}: {e}"[:200]
+    to, ts = [], []
+    for _ in range(ROUNDS):
+        to.append(timeit(ours, iters))
+        if sdpa:
+            ts.append(timeit(theirs, iters))
+    rec = {"bench": "prefill_attn", "name": name, "B": B, "S": S, "pos": pos, "C": C, "H": H, "Hkv": HKV,
+           "kernel_us": round(med(to), 1), "kernel_us_minmax": [round(min(to), 1), round(max(to), 1)],
+           "kernel_TFs": round(flops(B, S, pos) / med(to) / 1e6, 1)}
+    if sdpa:
+        a, b = ours().float(), theirs().float()
+        rec.update({"sdpa_us": round(med(ts), 1), "sdpa_us_minmax": [round(min(ts), 1), round(max(ts), 1)],
+                    "sdpa_TFs": round(flops(B, S, pos) / med(ts) / 1e6, 1),
+                    "sdpa_mask": "is_causal" if mask is None else "explicit",
+                    "speedup_vs_sdpa": round(med(ts) / med(to), 3),
+                    "max_abs_diff": (a - b).abs().max().item(), "max_abs": b.abs().max().item()})
+    if err:
+        rec["sdpa_error"] = err
+    emit(rec)
+    return med(to)
+
+
+def model_rows(emit, batch, prompt, rounds):
+    cfg = PRESETS["llama3-8b"]
+    torch.manual_seed(0)
+    dec = LlamaDecoder(cfg, batch=batch, context=2 * prompt, device="cuda", fp8=True)
+    toks = torch.randint(0, cfg.vocab, (batch, prompt), device="cuda")
+    variants = [("sdpa", False, None), ("prefill_attn", True, None), ("prefill_attn+chunk256", True, 256)]
+    logits = {}
+    fwd = dec._forward
+
+    def spy(*a, **k):
+        r = fwd(*a, **k)
+        if r is not None:
+            logits[spy.key] = r[:, -1].float().clone()
+        return r
+
+    dec._forward = spy
+    kept = {}
+
+    def cos(a, b):
+        c = F.cosine_similarity(a, b, dim=-1)
+        return c.min().item(), c.mean().item()
+
+    for weights, tiled in (("fp8", False), ("fp8", True), ("bf16", False)):
+        dec.fp8, dec.prefill_tiled = weights == "fp8", tiled
+        times = {v[0]: [] for v in variants}
+        for r in range(rounds + 1):  # round 0 warms every variant
+            for key, pa, chunk in variants:
+                dec.prefill_attn, spy.key = pa, key
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                dec.prefill(toks, chunk=chunk)
+                torch.cuda.synchronize()
+                if r:
+                    times[key].append((time.perf_counter() - t1) * 1e3)
+        for key, _, _ in variants:
+            ts = times[key]
+            kept[(weights, tiled, key)] = logits[key]
+            cmin, cmean = cos(logits[key], logits["sdpa"])
+            emit({"bench": "llama3-8b-prefill", "weights": weights, "prefill_tiled": tiled, "attention": key,
+                  "batch": batch, "prompt": prompt, "ms": round(med(ts), 2),
+                  "ms_minmax": [round(min(ts), 2), round(max(ts), 2)],
+                  "tok_per_s": round(batch * prompt / med(ts) * 1e3),
+                  "speedup_vs_sdpa": round(med(times["sdpa"]) / med(ts), 3),
+                  "min_cos_logits_vs_sdpa": cmin, "mean_cos_logits_vs_sdpa": cmean})
+    # how far two stock paths of the same fp8 model are from each other: the
+    # yardstick for the cosines above (random weights, 32 layers of fp8 rounding)
+    cmin, cmean = cos(kept[("fp8", False, "sdpa")], kept[("fp8", True, "sdpa")])
+    emit({"bench": "llama3-8b-prefill-sensitivity", "what": "fp8 sdpa, sliced vs tiled linears (no new code)",
+          "min_cos_logits": cmin, "mean_cos_logits": cmean})
+    cmin, cmean = cos(kept[("fp8", False, "sdpa")], kept[("bf16", False, "sdpa")])
+    emit({"bench": "llama3-8b-prefill-sensitivity", "what": "sdpa, fp8 vs bf16 weights (no new code)",
+          "min_cos_logits": cmin, "mean_cos_logits": cmean})
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=100)
+    ap.add_argument("--out", default="")
+    ap.add_argument("--skip-model", action="store_true")
+    ap.add_argument("--skip-kernel", action="store_true")
+    a = ap.parse_args()
+    out = open(a.out, "a") if a.out else None
+
+    def emit(rec):
+        print(json.dumps(rec), flush=True)
+        if out:
+            out.write(json.dumps(rec) + "\n")
+            out.flush()
+
+    g = torch.Generator(device="cuda").manual_seed(0)
+    if not a.skip_kernel:
+        kernel_row(emit, g, a.iters, 8, 1024, 0, 2048, "llm5 prompt")
+        t0 = kernel_row(emit, g, a.iters, 1, 4096, 0, 8192, "4k prompt")
+        kernel_row(emit, g, a.iters, 1, 8192, 0, 8192, "8k prompt")
+        kernel_row(emit, g, a.iters, 1, 512, 7680, 8192, "chunk 512 at 7680")
+        t1 = kernel_row(emit, g, a.iters, 1, 4096, 4096, 8192, "4k chunk at 4096", sdpa=False)
+        # the (S 4096, pos 4096) call has 3x the unmasked keys of (S 4096, pos 0): a time
+        # ratio near 1 would mean the tiles above the diagonal are not skipped
+        emit({"bench": "prefill_attn_causal_skip", "t_pos0_over_t_pos4096": round(t0 / t1, 3), "work_ratio": 0.333})
+        torch.cuda.empty_cache()
+    if not a.skip_model:
+        model_rows(emit, 8, 1024, ROUNDS)
+
+
+if __name__ == "__main__":
+    main()
