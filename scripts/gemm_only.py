@@ -8,7 +8,7 @@ import torch  # noqa: E402
 from pbs_amd.ops import kernels as K  # noqa: E402
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
-opts = int(sys.argv[2]) if len(sys.argv) > 2 else 0
+opts = int(sys.argv[2]) if len(sys.argv) > 2 else -1  # -1: the default dealing
 K.lib().gpbs_hip_set_gemm_opts(opts)
 A = torch.randn(n, n, device="cuda", dtype=torch.bfloat16)
 B = torch.randn(n, n, device="cuda", dtype=torch.bfloat16)

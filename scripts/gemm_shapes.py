@@ -3,7 +3,7 @@
 CU at 4096^2) and K-loop rate.  Variants and torch interleaved per round in
 one process; median of rounds.
 
-    python scripts/gemm_shapes.py [--iters 20] [--opts 205064,2097192]
+    python scripts/gemm_shapes.py [--iters 20] [--opts 8,8388616]
 """
 import argparse
 import json
@@ -20,7 +20,7 @@ from scripts.kbench import timed  # noqa: E402
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--opts", default="205064,2097192")
+    ap.add_argument("--opts", default="8,8388616", help="gpbs_hip_set_gemm_opts values: default dealing vs static unit")
     ap.add_argument("--shapes", default="4096x4096x4096,4096x4096x8192,4096x4096x16384,8192x8192x8192")
     args = ap.parse_args()
     L = K.lib()
@@ -34,13 +34,14 @@ def main():
         Cm = torch.empty(m, n, device="cuda", dtype=torch.bfloat16)
         res = {o: [] for o in opts}
         res["torch"] = []
+        prev = L.gpbs_hip_set_gemm_opts(-1)
         for _ in range(5):
             for o in opts:
                 L.gpbs_hip_set_gemm_opts(o)
                 res[o].append(timed(lambda: L.gpbs_hip_gemm_bf16(K._ptr(A), K._ptr(B), K._ptr(Cm), m, n, k, K._ptr(q),
                                                                  None, 0, 0, None, None, 0, s), args.iters, q.zero_))
             res["torch"].append(timed(lambda: torch.mm(A, B.t(), out=Cm), args.iters))
-        L.gpbs_hip_set_gemm_opts(205064)
+        L.gpbs_hip_set_gemm_opts(prev)
         tmm = sorted(res["torch"])[2]
         for key, v in res.items():
             ms = sorted(v)[2]

@@ -114,29 +114,20 @@ def main():
     A = torch.randn(n, n, device=dev, dtype=torch.bfloat16)
     B = torch.randn(n, n, device=dev, dtype=torch.bfloat16)
     Cm = torch.empty(n, n, device=dev, dtype=torch.bfloat16)
-    # A/B of the tile queue (plain vs XCD-range), interleaved rounds in one
+    # A/B of the 256x256 kernel's tile dealing (gpbs_hip_set_gemm_opts; the
+    # removed schedule variants: docs/gemm_lab.md), interleaved rounds in one
     # process (cross-box timings are not comparable: DVFS).
-    names = {0: "plain-queue", 1: "xcd-range", 2: "deep-prefetch", 4: "staggered-groups",
-             12: "staggered-2d-blocks", 13: "staggered-xcd-range-2d-blocks"}
-    if os.environ.get("KBENCH_GEMM_ONLY"):
-        names = {4: "staggered-groups", 256 | 4096: "2phase-balanced", 256 | 8192: "2phase-own-a", 256 | 16384: "1phase",
-                 256 | 8192 | 32768: "2phase-own-a-mfma32",
-                 256 | 8192 | 65536: "2phase-own-a-lds-c",
-                 256 | 8192 | 65536 | 131072: "2phase-own-a-lds-c-nt",
-                 256 | 8192 | 65536 | 131072 | 8: "2phase-own-a-lds-c-nt-2d-blocks",
-                 256 | 8192 | 65536 | 131072 | 8 | 1: "2phase-own-a-lds-c-nt-2d-blocks-xcd-range",
-                 262144: "pipelined-1-barrier",
-                 524288: "pipelined-1-barrier-asm-reads",
-                 32: "4wave", 32 | (1 << 20): "4wave-agpr-acc"}
-        if os.environ.get("KBENCH_GEMM_VARIANTS"):  # comma-separated opts values
-            names = {int(v): names.get(int(v), str(v)) for v in os.environ["KBENCH_GEMM_VARIANTS"].split(",")}
+    names = {8: "2d-blocks", 0: "row-major", 1: "xcd-range", 9: "2d-blocks-xcd-range", 8 | 1 << 23: "2d-blocks-static"}
+    if os.environ.get("KBENCH_GEMM_VARIANTS"):  # comma-separated opts values
+        names = {int(v): names.get(int(v), str(v)) for v in os.environ["KBENCH_GEMM_VARIANTS"].split(",")}
     ab = {k: [] for k in names}
+    prev = L.gpbs_hip_set_gemm_opts(-1)
     for _ in range(5):
         for opt in names:
             L.gpbs_hip_set_gemm_opts(opt)
             ab[opt].append(timed(lambda: L.gpbs_hip_gemm_bf16(K._ptr(A), K._ptr(B), K._ptr(Cm), n, n, n, K._ptr(q),
                                                               None, 0, 0, None, None, 0, s), args.iters, zero))
-    L.gpbs_hip_set_gemm_opts(256 | 8192 | 65536 | 131072 | 8)
+    L.gpbs_hip_set_gemm_opts(prev)
     for opt, v in ab.items():
         ms = sorted(v)[len(v) // 2]
         out.append({"kernel": "gemm_bf16", "variant": names[opt], "shape": [n, n, n],
@@ -154,7 +145,7 @@ def main():
         err = (Cm[:512].float() - ref).abs().max().item()
         out.append({"kernel": "gemm_bf16", "variant": names[opt], "check_max_abs_err": err,
                     "ok": err < 0.02 * ref.abs().max().item()})
-    L.gpbs_hip_set_gemm_opts(256 | 8192 | 65536 | 131072 | 8)
+    L.gpbs_hip_set_gemm_opts(prev)
     if os.environ.get("KBENCH_GEMM_ONLY"):
         for r in out:
             print(json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in r.items()}))

@@ -21,8 +21,9 @@ def _lib():
     N.load_hip(required=True)
 
 
-# 128x128-tile path: (128,128,64), (256,384,512); 256x256 8-phase path (M, N %
-# 256 == 0): K-tile counts 1, 2, 3, 16 and 64 exercise prologue/tail waits.
+# 128x128-tile path: (128,128,64), (256,384,512); 256x256 path (M, N % 256 ==
+# 0; two phases per K-tile): K-tile counts 1, 2, 3, 16 and 64 exercise the
+# prologue and the last tile's waits.
 @pytest.mark.parametrize("M,Nn,Kd", [(128, 128, 64), (256, 384, 512), (256, 256, 64), (512, 768, 128),
                                      (768, 512, 192), (1024, 512, 1024), (4096, 4096, 4096)])
 def test_gemm_bf16_matches_fp32_reference(M, Nn, Kd):
@@ -182,25 +183,78 @@ def test_device_adapt_bit_exact_vs_host():
         assert bytes(got[k].numpy().tobytes()) == ref, k
 
 
-@pytest.mark.parametrize("opts", [0, 1, 2, 3, 4, 5, 16, 32, 256, 256 | 8, 256 | 9, 256 | 1024, 256 | 64, 256 | 4096, 256 | 4096 | 64, 256 | 8192, 256 | 8192 | 64, 256 | 8192 | 32768, 256 | 8192 | 65536, 256 | 8192 | 65536 | 131072, 256 | 16384, 256 | 16384 | 64, 262144, 524288,
-                                  256 | 8192 | 65536 | 131072 | 8, 256 | 8192 | 65536 | 131072 | 9,
-                                  32 | (1 << 20), 32 | (1 << 21), 32 | (1 << 21) | 8, 32 | (1 << 22), 32 | (1 << 22) | 8,
-                                  256 | 8192 | 65536 | 131072 | 8 | (1 << 23)])
-def test_gemm256_variants_match_reference(opts):
-    """Every 256x256 schedule variant (plain / XCD-range tile queue x one-half-
-    per-phase / deep prefetch; the 2-phase kernel -- the default -- with 2-D
-    XCD blocks, streaming C stores and its stamp build; the 4-wave kernels with
-    AGPR accumulators, bits 20-22) is exact against fp32 on prologue/tail shapes."""
+_G256_SHAPES = ((256, 256, 64), (512, 256, 128), (256, 512, 192), (1024, 768, 1024), (1024, 512, 512))
+_G256_DEFAULT = 8
+
+
+def _g256_operands(M, Nn, Kd):
+    g = torch.Generator(device="cuda").manual_seed(M * 7 + Kd)
+    A = torch.randn(M, Kd, device="cuda", dtype=torch.bfloat16, generator=g)
+    B = torch.randn(Nn, Kd, device="cuda", dtype=torch.bfloat16, generator=g)
+    return A, B
+
+
+@pytest.fixture(scope="module")
+def g256_default():
+    """Per shape: the fp32 reference and what the default dealing computes."""
+    L = K.lib()
+    old = L.gpbs_hip_set_gemm_opts(_G256_DEFAULT)
+    try:
+        res = {}
+        for shape in _G256_SHAPES:
+            A, B = _g256_operands(*shape)
+            res[shape] = (A.float() @ B.float().t(), K.gemm_bf16(A, B))
+        torch.cuda.synchronize()
+        return res
+    finally:
+        L.gpbs_hip_set_gemm_opts(old)
+
+
+# 8: 2-D per-XCD blocks (the default), 1: XCD-range tile queue, 0: row-major
+# dealing from the plain queue, bit 23: static unit, 205064: the default as
+# recorded command lines spell it.  (1024, 512, K) is the smallest shape at
+# which 2-D blocks engage; (1024, 768, 1024) is one where they fall back.
+_G256_LIVE = [8, 9, 0, 1, 8 | 1 << 23, 205064]
+# Values that recorded command lines and profiles carry: each selected a
+# schedule variant that is gone (docs/gemm_lab.md).  The setter keeps their
+# dealing bits and the shipped schedule runs, so they stay exact too.
+_G256_LEGACY = [2, 3, 4, 5, 16, 32, 256, 256 | 8, 256 | 9, 256 | 1024, 256 | 64, 256 | 4096, 256 | 4096 | 64, 256 | 8192,
+                256 | 8192 | 64, 256 | 8192 | 32768, 256 | 8192 | 65536, 256 | 8192 | 65536 | 131072, 256 | 16384,
+                256 | 16384 | 64, 262144, 524288, 256 | 8192 | 65536 | 131072 | 9, 32 | (1 << 20), 32 | (1 << 21),
+                32 | (1 << 21) | 8, 32 | (1 << 22), 32 | (1 << 22) | 8, 256 | 8192 | 65536 | 131072 | 8 | (1 << 23)]
+
+
+@pytest.mark.parametrize("opts", _G256_LIVE + _G256_LEGACY)
+def test_gemm256_variants_match_reference(opts, g256_default):
+    """Every tile dealing of the 256x256 kernel, under its live and its
+    legacy spellings, is exact against fp32 on prologue/tail shapes and
+    bit-identical to the default dealing: dealing changes which workgroup
+    computes a tile, never the arithmetic."""
     L = K.lib()
     old = L.gpbs_hip_set_gemm_opts(opts)
     try:
-        for M, Nn, Kd in ((256, 256, 64), (512, 256, 128), (256, 512, 192), (1024, 768, 1024), (1024, 512, 512)):
-            g = torch.Generator(device="cuda").manual_seed(M * 7 + Kd)
-            A = torch.randn(M, Kd, device="cuda", dtype=torch.bfloat16, generator=g)
-            B = torch.randn(Nn, Kd, device="cuda", dtype=torch.bfloat16, generator=g)
+        assert L.gpbs_hip_set_gemm_opts(-1) == opts & (1 | 8 | 1 << 23)
+        for M, Nn, Kd in _G256_SHAPES:
+            A, B = _g256_operands(M, Nn, Kd)
             out = K.gemm_bf16(A, B)
-            ref = A.float() @ B.float().t()
+            ref, dflt = g256_default[(M, Nn, Kd)]
             err = (out.float() - ref).abs().max().item()
             assert err < 2e-2 * ref.abs().max().item() + 1e-2, (opts, M, Nn, Kd, err)
+            assert torch.equal(out, dflt), (opts, M, Nn, Kd)
+    finally:
+        L.gpbs_hip_set_gemm_opts(old)
+
+
+def test_gemm_opts_setter_normalises():
+    """The setter stores the live dealing bits only: the bits that spell the
+    shipped schedule are dropped silently, bits of removed variants with one
+    line on stderr, and a negative value only queries."""
+    L = K.lib()
+    old = L.gpbs_hip_set_gemm_opts(-1)
+    try:
+        L.gpbs_hip_set_gemm_opts(32 | 1 << 21)
+        assert L.gpbs_hip_set_gemm_opts(-1) == 0
+        L.gpbs_hip_set_gemm_opts(205065)
+        assert L.gpbs_hip_set_gemm_opts(-1) == 9
     finally:
         L.gpbs_hip_set_gemm_opts(old)
