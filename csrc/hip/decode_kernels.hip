@@ -9,9 +9,11 @@
 //                      launches, 2 index_copy_ and their transposes)
 //   k_decode_attn    : grouped-query attention of the new token over cache rows
 //                      0..pos: one workgroup per (batch, KV head), the G query
-//                      heads of the group share every K/V row read; 4 waves split
-//                      the keys (a lane owns a key for QK^T, a lane owns 2 dims
-//                      for PV), online softmax, wave partials merged in LDS.
+//                      heads of the group share every K/V row read; 8 waves split
+//                      the keys in 64-key steps (a lane owns a key for QK^T; for
+//                      PV a lane owns 8 dims of every 4th key), online softmax,
+//                      wave partials merged in LDS; with nsplit > 1 the keys are
+//                      split over workgroups too and k_decode_attn_combine merges.
 #include <algorithm>
 
 #include "common.hpp"

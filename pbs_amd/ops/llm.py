@@ -76,17 +76,32 @@ def rope_dpos(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos_t: torc
     return y
 
 
+def _need_dpos(pos_t: torch.Tensor, what: str):
+    """The device-resident position of the graph-captured decode step: one int32
+    on the GPU.  Only the host side is checked; reading the value would force a
+    sync inside a captured graph."""
+    if not isinstance(pos_t, torch.Tensor) or pos_t.dtype != torch.int32 or pos_t.numel() != 1:
+        raise ValueError(f"{what}: pos_t must be a 1-element int32 tensor, got "
+                         f"{getattr(pos_t, 'dtype', type(pos_t))} {tuple(getattr(pos_t, 'shape', ()))}")
+    if not pos_t.is_cuda:
+        raise ValueError(f"{what}: pos_t must be a CUDA tensor (the kernel reads it), got {pos_t.device}")
+
+
 def qkv_rope_cache(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos_t: torch.Tensor, kc: torch.Tensor,
                    vc: torch.Tensor, n_heads: int) -> torch.Tensor:
     """One-token decode: split the packed qkv [B, 1, (H + 2 Hkv) hd], RoPE q and k
     at the device position pos_t (int32 [1]), write k / v into the caches
-    [B, Hkv, C, hd] at that row, return q [B, H, hd]."""
+    [B, Hkv, C, hd] at that row, return q [B, H, hd].  No bounds check on the
+    device value: the caller keeps 0 <= pos < C."""
+    if kc.dim() != 4 or vc.shape != kc.shape:
+        raise ValueError(f"qkv_rope_cache: caches {tuple(kc.shape)} / {tuple(vc.shape)} must be [B, Hkv, C, hd] of "
+                         f"one shape")
     B, Hkv, Cn, hd = kc.shape
+    _need_dpos(pos_t, "qkv_rope_cache")
     _need(qkv, "qkv_rope_cache qkv")
     _need(kc, "qkv_rope_cache kc")
     _need(vc, "qkv_rope_cache vc")
-    if qkv.numel() != B * (n_heads + 2 * Hkv) * hd or vc.shape != kc.shape or cos.shape[-1] * 2 != hd \
-            or pos_t.dtype != torch.int32:
+    if qkv.numel() != B * (n_heads + 2 * Hkv) * hd or vc.shape != kc.shape or cos.shape[-1] * 2 != hd:
         raise ValueError(f"qkv_rope_cache: qkv {tuple(qkv.shape)} vs cache {tuple(kc.shape)}, H={n_heads}")
     # the kernel indexes the RoPE tables and the cache rows with the device
     # position: the tables must cover every cache row, dtypes as it assumes
@@ -106,12 +121,31 @@ def decode_attn(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, pos_t: torc
     0..pos (pos_t int32 [1] on device): q [B, H, 128] -> [B, H * 128].  The keys
     are split over `nsplit` workgroups per (batch, KV head) (flash-decoding,
     default: enough to give the chip >= 256 workgroups) and merged by a combine
-    kernel."""
+    kernel.  Everything the kernel takes as a raw pointer is checked on the host
+    tensors before the library is touched, except the device value of pos_t:
+    reading it would force a sync inside a captured graph, so the caller keeps
+    0 <= pos (the kernel clamps pos + 1 to C)."""
+    if q.dim() != 3 or kc.dim() != 4 or vc.shape != kc.shape:
+        raise ValueError(f"decode_attn: q {tuple(q.shape)} must be [B, H, 128], caches {tuple(kc.shape)} / "
+                         f"{tuple(vc.shape)} [B, Hkv, C, 128] of one shape")
     B, Hkv, Cn, hd = kc.shape
     H = q.shape[1]
+    if hd != 128 or B < 1 or Hkv < 1 or Cn < 1 or q.shape != (B, H, hd):
+        raise ValueError(f"decode_attn: q {tuple(q.shape)} must be [B, H, 128] for caches {tuple(kc.shape)} "
+                         f"[B, Hkv, C, 128]")
+    if H % Hkv or (H // Hkv) not in (1, 2, 4, 8):
+        raise ValueError(f"decode_attn: group size H / Hkv = {H} / {Hkv} must be 1, 2, 4 or 8")
+    for name, t in (("q", q), ("kc", kc), ("vc", vc)):
+        if t.dtype != torch.bfloat16:
+            raise ValueError(f"decode_attn: {name} must be bf16, got {t.dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"decode_attn: {name} must be contiguous (strides {t.stride()})")
+    if nsplit is not None and (not isinstance(nsplit, int) or isinstance(nsplit, bool) or nsplit < 1):
+        raise ValueError(f"decode_attn: nsplit={nsplit!r} must be None or an int >= 1")
+    _need_dpos(pos_t, "decode_attn")
     _need(q, "decode_attn q")
-    if hd != 128 or H % Hkv or (H // Hkv) not in (1, 2, 4, 8) or q.shape != (B, H, hd):
-        raise ValueError(f"decode_attn: q {tuple(q.shape)}, cache {tuple(kc.shape)} (head_dim 128, G in 1/2/4/8)")
+    _need(kc, "decode_attn kc")
+    _need(vc, "decode_attn vc")
     out = torch.empty(B, H * hd, dtype=torch.bfloat16, device=q.device)
     if nsplit is None:
         nsplit = max(1, min(8, -(-256 // (B * Hkv)), -(-Cn // 64)))
