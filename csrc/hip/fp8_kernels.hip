@@ -17,6 +17,11 @@
 // L2) uses the SAME lane -> k permutation, so each MFMA sums a consistent set of 32
 // k's and the product is exact regardless of the hardware's in-fragment k order.
 // The eight wave partials are reduced through LDS.
+//
+// The quantisers (k_quant_rows_fp8, k_rmsnorm_quant_fp8, k_swiglu_quant_fp8):
+// inputs must be finite; behaviour differs otherwise from the Python reference
+// (llm.quant_rows_fp8_ref): the clamp fminf(fmaxf(v, -448), 448) turns a NaN
+// into -448, the reference yields a NaN code.
 #include "common.hpp"
 
 namespace gpbs_fp8 {

@@ -272,11 +272,20 @@ def quant_rows_fp8(x: torch.Tensor):
 
 
 def quant_rows_fp8_ref(x: torch.Tensor):
-    """fp32 PyTorch reference of quant_rows_fp8 (runs on CPU too)."""
+    """fp32 PyTorch reference of quant_rows_fp8 (runs on CPU too).  It mirrors the
+    kernel's arithmetic (x * (448 / amax) in fp32, clamp, round to nearest even),
+    so on finite input the codes and scales agree bit for bit.  Inputs must be
+    finite; behaviour differs otherwise (a NaN becomes a NaN code here and -448
+    in the kernel's clamp)."""
     xf = x.float()
     amax = xf.abs().amax(-1)
-    s = torch.where(amax > 0, amax / FP8_MAX, torch.ones_like(amax))
-    inv = torch.where(amax > 0, FP8_MAX / amax, torch.ones_like(amax))  # multiply, as the kernel does
+    # Both quotients as tensor / tensor: one correctly rounded division each, as in
+    # the kernel.  torch evaluates `scalar / tensor` as reciprocal(tensor) * scalar
+    # (two roundings, which moves values onto and off e4m3 ties) and, on the GPU,
+    # `tensor / scalar` as tensor * (1 / scalar).
+    top = torch.full_like(amax, FP8_MAX)
+    s = torch.where(amax > 0, amax / top, torch.ones_like(amax))
+    inv = torch.where(amax > 0, top / amax, torch.ones_like(amax))  # multiply, as the kernel does
     q = (xf * inv.unsqueeze(-1)).clamp(-FP8_MAX, FP8_MAX).to(torch.float8_e4m3fn)
     return q, s
 
@@ -291,6 +300,23 @@ class Fp8Weight:
             raise ValueError(f"Fp8Weight: [N={self.N}, K={self.K}] needs N % 16 == 0 and K % 256 == 0")
         q, self.s = quant_rows_fp8(w) if w.is_cuda else quant_rows_fp8_ref(w)
         self.qs = self.shuffle(q)  # the only stored copy: the kernel's lane-order layout
+
+    @classmethod
+    def from_quantised(cls, q: torch.Tensor, s: torch.Tensor) -> "Fp8Weight":
+        """The weight of given row-major e4m3fn codes q [N, K] and fp32 row scales
+        s [N] (no quantiser involved): only the shuffled copy is built."""
+        if q.dtype != torch.float8_e4m3fn or q.dim() != 2:
+            raise ValueError(f"Fp8Weight.from_quantised: q must be e4m3fn [N, K], got {q.dtype} {tuple(q.shape)}")
+        self = cls.__new__(cls)
+        self.N, self.K = q.shape
+        if self.N % 16 or self.K % 256:
+            raise ValueError(f"Fp8Weight: [N={self.N}, K={self.K}] needs N % 16 == 0 and K % 256 == 0")
+        if s.dtype != torch.float32 or s.numel() != self.N or s.device != q.device:
+            raise ValueError(f"Fp8Weight.from_quantised: s must be fp32 with {self.N} elements on {q.device}, got "
+                             f"{s.dtype} {tuple(s.shape)} on {s.device}")
+        self.s = s.reshape(self.N).contiguous()
+        self.qs = self.shuffle(q.contiguous())
+        return self
 
     # Kernel layout: [N/16 strips][K/256 blocks][4 steps u][4 lane groups g][16 rows r][16 B];
     # lane l = 16 g + r of the wave that owns (strip, block) reads the 16 bytes
@@ -326,11 +352,26 @@ def fp8_linear_q(xq: torch.Tensor, sx: torch.Tensor, w: Fp8Weight, resid: Option
     already-quantised rows (the output of quant_rows_fp8 / rmsnorm_quant_fp8 /
     swiglu_quant_fp8); bf16 out.  ``tiled`` (opt-in, no resid, N % 128 == 0):
     one launch of the LDS-tiled fp8 GEMM over the shuffled weight for any M,
-    instead of one weight-streaming launch per 64 rows."""
+    instead of one weight-streaming launch per 64 rows.  The library takes raw
+    pointers, so everything it reads is checked here first."""
     lead = xq.shape[:-1]
     if xq.dtype != torch.float8_e4m3fn or xq.shape[-1] != w.K or not xq.is_contiguous():
         raise ValueError(f"fp8_linear_q: need contiguous e4m3fn [..., {w.K}], got {xq.dtype} {tuple(xq.shape)}")
     M = xq.numel() // w.K
+    if M == 0:
+        raise ValueError(f"fp8_linear_q: xq {tuple(xq.shape)} has no rows")
+    if sx.dtype != torch.float32 or not sx.is_contiguous() or sx.numel() != M:
+        raise ValueError(f"fp8_linear_q: sx must be contiguous fp32 with {M} elements, got {sx.dtype} "
+                         f"{tuple(sx.shape)} contiguous={sx.is_contiguous()}")
+    if resid is not None and (resid.dtype != torch.bfloat16 or not resid.is_contiguous()
+                              or resid.numel() != M * w.N):
+        raise ValueError(f"fp8_linear_q: resid must be contiguous bf16 with {M} x {w.N} elements, got {resid.dtype} "
+                         f"{tuple(resid.shape)} contiguous={resid.is_contiguous()}")
+    for name, t in (("xq", xq), ("sx", sx), ("weight", w.qs), ("weight scale", w.s), ("resid", resid)):
+        if t is not None and not t.is_cuda:
+            raise ValueError(f"fp8_linear_q: {name} must be a CUDA tensor, got {t.device}")
+        if t is not None and t.device != xq.device:
+            raise ValueError(f"fp8_linear_q: {name} is on {t.device}, xq on {xq.device}")
     y = torch.empty(*lead, w.N, dtype=torch.bfloat16, device=xq.device)
     if tiled and resid is None and w.N % 128 == 0:
         gemm_fp8(xq.view(M, w.K), sx.reshape(M), w.qs, w.s, y.view(M, w.N), b_shuffled=True)
