@@ -1,0 +1,197 @@
+// The decode attention kernel and its combine kernel.  Not a header of its own:
+// decode_kernels.hip includes this text twice, inside namespace gpbs_dec, with
+// GPBS_SEQ 0 (k_decode_attn, k_decode_attn_combine: one device position for
+// the batch) and GPBS_SEQ 1 (k_decode_attn_seq, k_decode_attn_combine_seq: dpos
+// is int32 [B]; sequence b has L = dpos[b] + 1 keys if 0 <= dpos[b] < C and is
+// idle otherwise: L = 0, no key loop, zero output).  Everything outside the
+// #if blocks is shared, so an active sequence gets the uniform kernel's bits.
+#if GPBS_SEQ
+#define GPBS_DEC_ATTN k_decode_attn_seq
+#define GPBS_DEC_COMBINE k_decode_attn_combine_seq
+#else
+#define GPBS_DEC_ATTN k_decode_attn
+#define GPBS_DEC_COMBINE k_decode_attn_combine
+#endif
+
+// q [B, H, 128], caches [B, Hkv, C, 128], out [B, H * 128]; H = G * Hkv.
+template <int G>
+__global__ __launch_bounds__(kAttnWaves * 64) void GPBS_DEC_ATTN(const u32x4* __restrict__ q,
+                                                               const u32x4* __restrict__ kc,
+                                                               const u32* __restrict__ vc,
+                                                               const int* __restrict__ dpos, u32* __restrict__ out,
+                                                               float* __restrict__ ws, int Hkv, int C, float scale,
+                                                               int nsplit) {
+  __shared__ float qs[G][kHd];
+  __shared__ float ms[kAttnWaves][G], ls[kAttnWaves][G];
+  __shared__ float os[kAttnWaves][G][kHd];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int split = blockIdx.x % nsplit, bh = blockIdx.x / nsplit;
+  const int b = bh / Hkv, kvh = bh % Hkv;
+#if GPBS_SEQ
+  const int pb = dpos[b];
+  const int L = (pb >= 0 && pb < C) ? pb + 1 : 0;  // keys 0..pos[b]; an idle slot has none
+#else
+  const int L = min(*dpos + 1, C);  // keys 0..pos
+#endif
+  // flash-decoding split: this workgroup takes keys [k0, k1) (64-aligned chunks)
+  const int chunk = ((L + nsplit - 1) / nsplit + 63) & ~63;
+  const int k0 = split * chunk, k1 = min(L, k0 + chunk);
+  const int H = G * Hkv;
+  // stage the group's queries (pre-scaled) in LDS: read as broadcasts below
+  for (int e = threadIdx.x; e < G * kHd / 8; e += kAttnWaves * 64) {
+    const int g = e / (kHd / 8), c = e % (kHd / 8);
+    const u32x4 v = q[((size_t)b * H + kvh * G + g) * (kHd / 8) + c];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      qs[g][c * 8 + 2 * k] = bfl(v[k]) * scale;
+      qs[g][c * 8 + 2 * k + 1] = bfh(v[k]) * scale;
+    }
+  }
+  __syncthreads();
+  const size_t head = (size_t)b * Hkv + kvh;
+  const u32x4* kh = kc + head * C * (kHd / 8);
+  const u32* vh = vc + head * C * (kHd / 2);
+  // PV lane map: key group kg = lane >> 4 takes keys kg, kg + 4, ...; dl = lane & 15
+  // owns dims 8 dl .. 8 dl + 7 (one 16-byte V load per key)
+  const int kg = lane >> 4, dl = lane & 15;
+  float m[G], l[G], o[G][8];
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    m[g] = -INFINITY, l[g] = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[g][e] = 0.f;
+  }
+
+  for (int base = k0 + w * 64; base < k1; base += kAttnWaves * 64) {
+    const int j = base + lane;
+    float s[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) s[g] = 0.f;
+    // opaque zero: keeps the (loop-invariant) LDS query reads inside this loop, so
+    // the compiler does not hoist G x 128 floats into registers and spill
+    int z = 0;
+    asm volatile("" : "+s"(z));
+    const float* qz = &qs[0][0] + z;
+    if (j < k1) {
+      const u32x4* kr = kh + (size_t)j * (kHd / 8);
+      u32x4 krow[kHd / 8];  // the lane's whole 256-byte key row in flight at once
+#pragma unroll
+      for (int c = 0; c < kHd / 8; ++c) krow[c] = kr[c];
+#pragma unroll
+      for (int c = 0; c < kHd / 8; ++c) {
+        const u32x4 kv = krow[c];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const float k0 = bfl(kv[k]), k1 = bfh(kv[k]);
+#pragma unroll
+          for (int g = 0; g < G; ++g) s[g] += qz[g * kHd + c * 8 + 2 * k] * k0 + qz[g * kHd + c * 8 + 2 * k + 1] * k1;
+        }
+      }
+    }
+    const int nk = min(64, k1 - base);
+    float p[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      const float sg = j < k1 ? s[g] : -INFINITY;
+      const float mn = fmaxf(m[g], wmax(sg));
+      const float corr = __expf(m[g] - mn);
+      p[g] = j < k1 ? __expf(sg - mn) : 0.f;
+      l[g] = l[g] * corr + wsum(p[g]);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[g][e] *= corr;
+      m[g] = mn;
+    }
+    // PV: 16 rounds of 4 keys (one per key group), 16-byte V loads, weights by shuffle
+    const u32x4* vb = reinterpret_cast<const u32x4*>(vh) + (size_t)base * (kHd / 8) + dl;
+#pragma unroll 4
+    for (int t = 0; t < 16; ++t) {
+      const int jj = 4 * t + kg;
+      float pj[G];
+#pragma unroll
+      for (int g = 0; g < G; ++g) pj[g] = __shfl(p[g], jj, 64);
+      if (jj < nk) {
+        const u32x4 vv = vb[(size_t)jj * (kHd / 8)];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float v0 = bfl(vv[e]), v1 = bfh(vv[e]);
+#pragma unroll
+          for (int g = 0; g < G; ++g) {
+            o[g][2 * e] += pj[g] * v0;
+            o[g][2 * e + 1] += pj[g] * v1;
+          }
+        }
+      }
+    }
+  }
+  // sum the 4 key groups' partials (lanes dl, dl + 16, dl + 32, dl + 48)
+#pragma unroll
+  for (int g = 0; g < G; ++g)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      o[g][e] += __shfl_xor(o[g][e], 16, 64);
+      o[g][e] += __shfl_xor(o[g][e], 32, 64);
+    }
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    if (kg == 0)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) os[w][g][8 * dl + e] = o[g][e];
+    if (lane == 0) ms[w][g] = m[g], ls[w][g] = l[g];
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < G * 64; e += kAttnWaves * 64) {
+    const int g = e / 64, d = 2 * (e % 64);
+    float M = -INFINITY;
+#pragma unroll
+    for (int v = 0; v < kAttnWaves; ++v) M = fmaxf(M, ms[v][g]);
+    float Ls = 0.f, a0 = 0.f, a1 = 0.f;
+#pragma unroll
+    for (int v = 0; v < kAttnWaves; ++v) {
+      const float f = ms[v][g] == -INFINITY ? 0.f : __expf(ms[v][g] - M);
+      Ls += ls[v][g] * f;
+      a0 += os[v][g][d] * f;
+      a1 += os[v][g][d + 1] * f;
+    }
+    if (nsplit == 1) {
+#if GPBS_SEQ
+      const float inv = Ls == 0.f ? 0.f : 1.f / Ls;  // idle: zero bits, not 0 * inf
+#else
+      const float inv = 1.f / Ls;
+#endif
+      out[((size_t)b * H + kvh * G + g) * (kHd / 2) + d / 2] = pack2(a0 * inv, a1 * inv);
+    } else {  // partial (max, sum, unnormalised o) for k_decode_attn_combine
+      float* p = ws + ((size_t)blockIdx.x * G + g) * (kHd + 2);
+      p[d] = a0;
+      p[d + 1] = a1;
+      if (d == 0) p[kHd] = M, p[kHd + 1] = Ls;
+    }
+  }
+}
+
+// Merge the nsplit partials of each (batch, KV head): grid B * Hkv, G * 64 threads.
+__global__ __launch_bounds__(512) void GPBS_DEC_COMBINE(const float* __restrict__ ws, u32* __restrict__ out,
+                                                             int Hkv, int G, int nsplit) {
+  const int bh = blockIdx.x, b = bh / Hkv, kvh = bh % Hkv;
+  const int g = threadIdx.x / 64, d = 2 * (threadIdx.x % 64);
+  if (g >= G) return;
+  float M = -INFINITY;
+  for (int sp = 0; sp < nsplit; ++sp) M = fmaxf(M, ws[(((size_t)bh * nsplit + sp) * G + g) * (kHd + 2) + kHd]);
+  float Ls = 0.f, a0 = 0.f, a1 = 0.f;
+  for (int sp = 0; sp < nsplit; ++sp) {
+    const float* p = ws + (((size_t)bh * nsplit + sp) * G + g) * (kHd + 2);
+    const float f = p[kHd] == -INFINITY ? 0.f : __expf(p[kHd] - M);
+    Ls += p[kHd + 1] * f;
+    a0 += p[d] * f;
+    a1 += p[d + 1] * f;
+  }
+#if GPBS_SEQ
+  const float inv = Ls == 0.f ? 0.f : 1.f / Ls;  // every partial of an idle sequence has Ls == 0
+#else
+  const float inv = 1.f / Ls;
+#endif
+  out[((size_t)b * Hkv * G + kvh * G + g) * (kHd / 2) + d / 2] = pack2(a0 * inv, a1 * inv);
+}
+
+#undef GPBS_DEC_ATTN
+#undef GPBS_DEC_COMBINE
+

@@ -47,6 +47,15 @@
 // epilogue.  Every tile rescales (no deferred rescale).  Keys ascend and key 0 is
 // visible to every query, so a row's max is finite after the first tile.  No
 // workspace, no atomics: equal inputs give equal bits.
+//
+// The _seq forms take a position and a length per sequence (int32 [B] each):
+// sequence b contributes n_b = min(len[b], S, C - pos[b]) tokens at cache rows
+// pos[b] .. pos[b] + n_b - 1, or none if pos[b] is outside [0, C) or len[b] <= 0.
+// The launch is sized for S; tokens s >= n_b are padding: they write no cache
+// row, their q / out rows are zero, and no q row >= n_b or cache row past
+// pos[b] + n_b - 1 is addressed.  The tile walk of a workgroup depends on its
+// sequence alone, so sequence b gets the bits of the uniform kernel run on it
+// alone with (S = n_b, pos = pos[b]).
 #include <algorithm>
 #include <climits>
 
@@ -95,6 +104,51 @@ __global__ __launch_bounds__(256) void k_qkv_rope_cache_prefill(const u32x4* __r
   }
 }
 
+// tokens that sequence b really has in a ragged launch of S (0: idle slot)
+__device__ __forceinline__ int seq_tokens(int pos, int len, int S, int C) {
+  return (pos < 0 || pos >= C || len <= 0) ? 0 : min(min(len, S), C - pos);
+}
+
+__global__ __launch_bounds__(256) void k_qkv_rope_cache_prefill_seq(const u32x4* __restrict__ qkv,
+                                                                    const float* __restrict__ cosb,
+                                                                    const float* __restrict__ sinb,
+                                                                    const int* __restrict__ posb,
+                                                                    const int* __restrict__ lenb,
+                                                                    u32x4* __restrict__ qo, u32x4* __restrict__ kc,
+                                                                    u32x4* __restrict__ vc, int B, int S, int H,
+                                                                    int Hkv, int C, int hd) {
+  const int per_head = hd / 8, heads = H + 2 * Hkv;
+  const size_t n8 = (size_t)B * S * heads * per_head;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (size_t)gridDim.x * blockDim.x) {
+    const int c = (int)(i % per_head);
+    const int hh = (int)((i / per_head) % heads);
+    const size_t bs = i / per_head / heads;
+    const int s = (int)(bs % S), b = (int)(bs / S);
+    const int pos = posb[b];
+    if (s >= seq_tokens(pos, lenb[b], S, C)) {  // padding token
+      if (hh < H) qo[(bs * H + hh) * per_head + c] = u32x4{0u, 0u, 0u, 0u};
+      continue;
+    }
+    const u32x4 v = qkv[i];
+    if (hh >= H + Hkv) {  // v: plain copy into the cache row
+      vc[(((size_t)b * Hkv + (hh - H - Hkv)) * C + pos + s) * per_head + c] = v;
+      continue;
+    }
+    const float* cr = cosb + (size_t)(pos + s) * (hd / 2) + c * 4;
+    const float* sr = sinb + (size_t)(pos + s) * (hd / 2) + c * 4;
+    u32x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float a = bfl(v[e]), bb = bfh(v[e]), cs = cr[e], sn = sr[e];
+      o[e] = pack2(a * cs - bb * sn, a * sn + bb * cs);
+    }
+    if (hh < H)
+      qo[(bs * H + hh) * per_head + c] = o;
+    else
+      kc[(((size_t)b * Hkv + (hh - H)) * C + pos + s) * per_head + c] = o;
+  }
+}
+
 constexpr int kHd = 128;
 constexpr int kWaves = 8;
 constexpr int kRows = kWaves * 32;  // query rows (token x head of the group) per workgroup
@@ -110,169 +164,15 @@ __device__ __forceinline__ int img_off(int r, int ch) { return 256 * r + 16 * (c
 
 __device__ __forceinline__ float ex2(float x) { return __builtin_amdgcn_exp2f(x); }
 
-// q [B, S, H, 128], caches [B, Hkv, C, 128], out [B, S, H * 128]; H = G * Hkv.
-template <int G>
-__global__ __launch_bounds__(kWaves * 64) void k_prefill_attn(const u32x4* __restrict__ q,
-                                                              const u32x4* __restrict__ kc,
-                                                              const u32x4* __restrict__ vc, u32x2* __restrict__ out,
-                                                              int S, int Hkv, int C, int pos, float scale_log2e,
-                                                              int nbh) {
-  __shared__ __attribute__((aligned(16))) unsigned char lds[2 * kTileBytes];  // K image, V image
-  constexpr int TPW = kRows / G;  // tokens per workgroup (a multiple of 32)
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int bh = blockIdx.x % nbh, qt = gridDim.x / nbh - 1 - blockIdx.x / nbh;  // heaviest query tiles first
-  const int b = bh / Hkv, kvh = bh % Hkv, H = G * Hkv;
-  const int q0 = qt * TPW;
-  const int c = lane & 31, h = lane >> 5;
-  const int g = (32 * w) / TPW, t0 = q0 + (32 * w) % TPW;  // the wave's head and first token
-  const bool wave_on = t0 < S;
-  const int s_raw = t0 + c;
-  const int s = min(s_raw, S - 1);          // padding rows repeat token S - 1 and are not stored
-  const int lim = pos + s;                  // last key this lane's query sees
-  const int wave_kmin = pos + t0;           // smallest lim of the wave
-  const int wave_kmax = pos + min(t0 + 31, S - 1);
-  const int ntiles = (pos + min(q0 + TPW - 1, S - 1)) / kKT + 1;
-  const int krow_last = pos + S - 1;        // <= C - 1: no address beyond it is formed
-
-  bf16x8 qf[8];
-  {
-    const u32x4* qp = q + (((size_t)b * S + s) * H + kvh * G + g) * (kHd / 8) + h;
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks) qf[ks] = __builtin_bit_cast(bf16x8, qp[2 * ks]);
-  }
-
-  // staging: piece i of this thread is chunk sch of tile row srow + 32 i
-  const int srow = tid >> 4, sch = tid & 15;
-  const size_t head = ((size_t)b * Hkv + kvh) * C;
-  u32x4 kr[2], vr[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const size_t row = head + min(srow + 32 * i, krow_last);
-    kr[i] = kc[row * (kHd / 8) + sch];
-    vr[i] = vc[row * (kHd / 8) + sch];
-  }
-
-  // K row reads: row 32 kt + c, chunk 2 ks + h
-  const int kx = ((c & 3) << 2) | ((c >> 2) & 3);
-  // V transposed reads: lane 4 qq + p of a 16-lane group gives row qq, dims 4 p .. 4 p + 3 of the block
-  const int gi = lane >> 4, qq = (lane >> 2) & 3, p = lane & 3;
-  const int vcl = 2 * (gi & 1) + (p >> 1);  // chunk within the 32-dim tile dt
-  int vbase[2], vx[2];
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    const int row = 4 * h + 8 * u + qq;  // + 32 kt + 16 s2
-    vbase[u] = kTileBytes + 256 * row + 8 * (p & 1);
-    vx[u] = ((row & 3) << 2) | ((row >> 2) & 3);
-  }
-
-  f32x16 o[4];
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) o[dt][i] = 0.f;
-  float m = -INFINITY, l = 0.f;
-
-  for (int t = 0; t < ntiles; ++t) {
-    __syncthreads();  // the previous tile's reads are done
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      *reinterpret_cast<u32x4*>(lds + img_off(srow + 32 * i, sch)) = kr[i];
-      *reinterpret_cast<u32x4*>(lds + kTileBytes + img_off(srow + 32 * i, sch)) = vr[i];
-    }
-    __syncthreads();
-    if (t + 1 < ntiles) {  // next tile in flight under this tile's MFMAs
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const size_t row = head + min((t + 1) * kKT + srow + 32 * i, krow_last);
-        kr[i] = kc[row * (kHd / 8) + sch];
-        vr[i] = vc[row * (kHd / 8) + sch];
-      }
-    }
-    const int k0 = t * kKT;
-    if (!wave_on || k0 > wave_kmax) continue;  // wave-uniform: tile wholly above this wave's diagonal
-
-    f32x16 sc[2];
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt) {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) sc[kt][i] = 0.f;
-#pragma unroll
-      for (int ks = 0; ks < 8; ++ks) {
-        const bf16x8 a = *reinterpret_cast<const bf16x8*>(lds + 256 * (32 * kt + c) + 16 * ((2 * ks + h) ^ kx));
-        sc[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, qf[ks], sc[kt], 0, 0, 0);
-      }
-    }
-    // scores in the log2 domain (a separate rounding: the max and the exponent see the same value)
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) sc[kt][i] = __fmul_rn(sc[kt][i], scale_log2e);
-    if (k0 + kKT - 1 > wave_kmin) {  // the tile crosses the wave's diagonal
-#pragma unroll
-      for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const int key = k0 + 32 * kt + (i & 3) + 8 * (i >> 2) + 4 * h;
-          sc[kt][i] = key <= lim ? sc[kt][i] : -INFINITY;
-        }
-    }
-    float tm = sc[0][0];
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) tm = fmaxf(tm, sc[kt][i]);
-    tm = fmaxf(tm, __shfl_xor(tm, 32, 64));
-    const float mn = fmaxf(m, tm);  // finite: key 0 is in the first tile and visible to every query
-    const float corr = ex2(m - mn);
-    m = mn;
-    l *= corr;
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) o[dt][i] *= corr;
-    bf16x8 pb[2][2];
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const __bf16 pv = (__bf16)ex2(sc[kt][i] - mn);
-        pb[kt][i >> 3][i & 7] = pv;
-        l += (float)pv;  // the value that multiplies V
-      }
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
-      int va[2];
-#pragma unroll
-      for (int u = 0; u < 2; ++u) va[u] = vbase[u] + 16 * ((4 * dt + vcl) ^ vx[u]);
-#pragma unroll
-      for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-          const int add = 256 * (32 * kt + 16 * s2);
-          const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(lds + va[0] + add));
-          const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(lds + va[1] + add));
-          const s16x8 a8 = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-          o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a8), pb[kt][s2], o[dt], 0, 0, 0);
-        }
-    }
-  }
-
-  if (!wave_on) return;
-  l += __shfl_xor(l, 32, 64);
-  if (s_raw >= S) return;
-  const float inv = 1.f / l;
-  u32x2* op = out + (((size_t)b * S + s) * H + kvh * G + g) * (kHd / 4) + h;
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {  // dims 32 dt + 8 j + 4 h .. + 3
-      u32x2 v;
-      v[0] = pack2(o[dt][4 * j] * inv, o[dt][4 * j + 1] * inv);
-      v[1] = pack2(o[dt][4 * j + 2] * inv, o[dt][4 * j + 3] * inv);
-      op[8 * dt + 2 * j] = v;
-    }
-}
+// k_prefill_attn<G> and its per-sequence form k_prefill_attn_seq<G> are one
+// source text compiled twice: the uniform kernel gets exactly the tokens it
+// always had.
+#define GPBS_SEQ 0
+#include "prefill_attn_body.hpp"
+#undef GPBS_SEQ
+#define GPBS_SEQ 1
+#include "prefill_attn_body.hpp"
+#undef GPBS_SEQ
 
 }  // namespace gpbs_pf
 
@@ -314,6 +214,45 @@ int gpbs_hip_prefill_attn(const void* q, const void* kc, const void* vc, void* o
     default: GPBS_PF_LAUNCH(8); break;
   }
 #undef GPBS_PF_LAUNCH
+  return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+int gpbs_hip_qkv_rope_cache_prefill_seq(const void* qkv, const float* cosb, const float* sinb, const int* posb,
+                                        const int* lenb, void* qo, void* kc, void* vc, int B, int S, int H, int Hkv,
+                                        int C, int hd, hipStream_t s) {
+  if (!qkv || !cosb || !sinb || !posb || !lenb || !qo || !kc || !vc || B <= 0 || S <= 0 || H <= 0 || Hkv <= 0 ||
+      C <= 0 || hd <= 0 || hd % 8)
+    return -22;
+  const size_t n8 = (size_t)B * S * (H + 2 * Hkv) * hd / 8;
+  const int grid = (int)std::min<size_t>((n8 + 255) / 256, 8192);
+  hipLaunchKernelGGL(k_qkv_rope_cache_prefill_seq, dim3(grid), dim3(256), 0, s, (const u32x4*)qkv, cosb, sinb, posb,
+                     lenb, (u32x4*)qo, (u32x4*)kc, (u32x4*)vc, B, S, H, Hkv, C, hd);
+  return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+// out must come in zeroed: rows s >= n_b are left as they are
+int gpbs_hip_prefill_attn_seq(const void* q, const void* kc, const void* vc, const int* posb, const int* lenb,
+                              void* out, int B, int S, int H, int Hkv, int C, int hd, float scale, hipStream_t s) {
+  if (!q || !kc || !vc || !posb || !lenb || !out || hd != kHd || B <= 0 || S <= 0 || H <= 0 || Hkv <= 0 ||
+      H % Hkv || C <= 0)
+    return -22;
+  const int G = H / Hkv;
+  if (G != 1 && G != 2 && G != 4 && G != 8) return -22;
+  const int tpw = kRows / G;
+  const long long nwg = (long long)((S + tpw - 1) / tpw) * B * Hkv;
+  if (nwg > INT_MAX) return -22;
+  const dim3 grid((unsigned)nwg), block(kWaves * 64);
+  const float sl = scale * 1.44269504088896340736f;
+#define GPBS_PF_SEQ_LAUNCH(g)                                                                                        \
+  hipLaunchKernelGGL(k_prefill_attn_seq<g>, grid, block, 0, s, (const u32x4*)q, (const u32x4*)kc, (const u32x4*)vc, \
+                     posb, lenb, (u32x2*)out, S, Hkv, C, sl, B * Hkv)
+  switch (G) {
+    case 1: GPBS_PF_SEQ_LAUNCH(1); break;
+    case 2: GPBS_PF_SEQ_LAUNCH(2); break;
+    case 4: GPBS_PF_SEQ_LAUNCH(4); break;
+    default: GPBS_PF_SEQ_LAUNCH(8); break;
+  }
+#undef GPBS_PF_SEQ_LAUNCH
   return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 

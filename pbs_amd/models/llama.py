@@ -72,6 +72,20 @@ def apply_rope_ref(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor) -> tor
     return torch.stack((a * c - b * s, a * s + b * c), dim=-1).flatten(-2).to(x.dtype)
 
 
+def apply_rope_seq_ref(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos) -> torch.Tensor:
+    """apply_rope_ref with one start position per sequence: token s of sequence b
+    is rotated at angle row pos[b] + s (clamped into the tables: rows of idle
+    slots and padding tokens are never used).  x [B, S, H, hd], cos/sin
+    [max_seq, hd/2], pos B ints.  Same arithmetic as apply_rope_ref."""
+    S = x.shape[1]
+    rows = torch.as_tensor(pos, device=x.device, dtype=torch.long)[:, None] + torch.arange(S, device=x.device)
+    rows = rows.clamp(0, cos.shape[0] - 1)
+    xf = x.float().unflatten(-1, (-1, 2))
+    a, b = xf[..., 0], xf[..., 1]
+    c, s = cos[rows][:, :, None, :], sin[rows][:, :, None, :]
+    return torch.stack((a * c - b * s, a * s + b * c), dim=-1).flatten(-2).to(x.dtype)
+
+
 class RMSNorm(nn.Module):
     def __init__(self, dim: int, eps: float):
         super().__init__()
@@ -98,12 +112,24 @@ class Block(nn.Module):
         self.w3 = nn.Linear(cfg.dim, cfg.ffn_dim, bias=False)  # up
         self.w2 = nn.Linear(cfg.ffn_dim, cfg.dim, bias=False)  # down
 
-    def attention(self, h, cos, sin, cache=None, pos: int = 0, fused: bool = False, prefill_attn: bool = False):
+    def attention(self, h, cos, sin, cache=None, pos: int = 0, fused: bool = False, prefill_attn: bool = False,
+                  seq=None):
         B, S, _ = h.shape
         cfg, hd = self.cfg, self.cfg.head_dim
         q = self.wq(h).view(B, S, cfg.n_heads, hd)
         k = self.wk(h).view(B, S, cfg.n_kv_heads, hd)
         v = self.wv(h).view(B, S, cfg.n_kv_heads, hd)
+        if seq is not None:  # ragged eager reference: host positions / lengths per sequence
+            from ..ops import llm
+            pos_b, lens = seq
+            kc, vc = cache
+            q, k = apply_rope_seq_ref(q, cos, sin, pos_b), apply_rope_seq_ref(k, cos, sin, pos_b)
+            for b in range(B):
+                n = llm.seq_tokens(pos_b[b], lens[b], S, kc.shape[2])
+                if n:
+                    kc[b, :, pos_b[b]:pos_b[b] + n] = k[b, :n].transpose(0, 1)
+                    vc[b, :, pos_b[b]:pos_b[b] + n] = v[b, :n].transpose(0, 1)
+            return self.wo(llm.attn_seq_ref(q, kc, vc, pos_b, lens).to(h.dtype))
         if fused:
             from ..ops import llm
             q, k = llm.rope(q, cos, sin, pos), llm.rope(k, cos, sin, pos)
@@ -139,13 +165,15 @@ class Block(nn.Module):
             "w2": llm.Fp8Weight(self.w2.weight),
         }
 
-    def forward_fp8(self, x, cos, sin, cache, pos: int, tiled: bool = False, prefill_attn: bool = False):
+    def forward_fp8(self, x, cos, sin, cache, pos: int, tiled: bool = False, prefill_attn: bool = False, seq=None):
         """Decode/prefill block on fp8 weights (fp8 MFMA linears + fused gfx950
         RMSNorm/RoPE/SwiGLU); inference only.  ``tiled``: the linears run the
         LDS-tiled fp8 GEMM (one launch for any M) where their N allows it.
         ``prefill_attn``: for S > 1 the attention block is two gfx950 launches
         (qkv_rope_cache_prefill, prefill_attn) instead of RoPE, cache copies and
-        SDPA."""
+        SDPA.  ``seq`` = (pos_t, len_t), int32 [B] device tensors: the ragged
+        form of those two launches, one position and length per sequence (any
+        S; ``pos`` is not used)."""
         from ..ops import llm
         cfg, hd, f = self.cfg, self.cfg.head_dim, self._fp8
         B, S, _ = x.shape
@@ -153,7 +181,10 @@ class Block(nn.Module):
                                tiled=tiled)
         nq, nkv = cfg.n_heads * hd, cfg.n_kv_heads * hd
         kc, vc = cache
-        if prefill_attn and S > 1:
+        if seq is not None:
+            q = llm.qkv_rope_cache_prefill_seq(qkv, cos, sin, seq[0], seq[1], kc, vc, cfg.n_heads)
+            o = llm.prefill_attn_seq(q, kc, vc, seq[0], seq[1])
+        elif prefill_attn and S > 1:
             q = llm.qkv_rope_cache_prefill(qkv, cos, sin, pos, kc, vc, cfg.n_heads)
             o = llm.prefill_attn(q, kc, vc, pos)
         else:
@@ -171,11 +202,13 @@ class Block(nn.Module):
                               tiled=tiled)
         return x + llm.fp8_linear_q(*llm.swiglu_quant_fp8(gu), f["w2"], tiled=tiled)
 
-    def decode_fp8_static(self, x, cos, sin, cache, pos_i32, pos_i64, mask):
+    def decode_fp8_static(self, x, cos, sin, cache, pos_i32, pos_i64, mask, pos_seq=None):
         """One-token decode with every shape static and the position on device
         (capturable in a HIP graph): the KV row is written with index_copy_ at
         pos, and attention runs over the whole static cache with an additive
-        mask, grouped per KV head (GQA without repeating K/V)."""
+        mask, grouped per KV head (GQA without repeating K/V).  ``pos_seq``
+        (int32 [B] on device, head_dim 128 only): one position per sequence,
+        idle slots write nothing; pos_i32 / pos_i64 / mask are not used."""
         from ..ops import llm
         cfg, hd, f = self.cfg, self.cfg.head_dim, self._fp8
         B = x.shape[0]
@@ -183,10 +216,15 @@ class Block(nn.Module):
         qkv = llm.fp8_linear_q(*llm.rmsnorm_quant_fp8(x, self.attn_norm.weight, self.attn_norm.eps), f["qkv"])
         nq, nkv = cfg.n_heads * hd, cfg.n_kv_heads * hd
         kc, vc = cache
-        if hd == 128 and G in (1, 2, 4, 8):  # fused gfx950 path: 2 launches between the qkv and o linears
-            q = llm.qkv_rope_cache(qkv, cos, sin, pos_i32, kc, vc, cfg.n_heads)
-            x = llm.fp8_linear_q(*llm.quant_rows_fp8(llm.decode_attn(q, kc, vc, pos_i32).view(B, 1, nq)), f["o"],
-                                 resid=x)
+        # fused gfx950 path: 2 launches between the qkv and o linears
+        if pos_seq is not None or (hd == 128 and G in (1, 2, 4, 8)):
+            if pos_seq is not None:
+                q = llm.qkv_rope_cache_seq(qkv, cos, sin, pos_seq, kc, vc, cfg.n_heads)
+                o = llm.decode_attn_seq(q, kc, vc, pos_seq)
+            else:
+                q = llm.qkv_rope_cache(qkv, cos, sin, pos_i32, kc, vc, cfg.n_heads)
+                o = llm.decode_attn(q, kc, vc, pos_i32)
+            x = llm.fp8_linear_q(*llm.quant_rows_fp8(o.view(B, 1, nq)), f["o"], resid=x)
             gu = llm.fp8_linear_q(*llm.rmsnorm_quant_fp8(x, self.mlp_norm.weight, self.mlp_norm.eps), f["w13"])
             return llm.fp8_linear_q(*llm.swiglu_quant_fp8(gu), f["w2"], resid=x)
         q = llm.rope_dpos(qkv[..., :nq].reshape(B, 1, cfg.n_heads, hd), cos, sin, pos_i32)
@@ -201,7 +239,12 @@ class Block(nn.Module):
         gu = llm.fp8_linear_q(*llm.rmsnorm_quant_fp8(x, self.mlp_norm.weight, self.mlp_norm.eps), f["w13"])
         return x + llm.fp8_linear_q(*llm.swiglu_quant_fp8(gu), f["w2"])
 
-    def forward(self, x, cos, sin, cache=None, pos: int = 0, fused: bool = False, prefill_attn: bool = False):
+    def forward(self, x, cos, sin, cache=None, pos: int = 0, fused: bool = False, prefill_attn: bool = False,
+                seq=None):
+        if seq is not None:  # ragged: the eager reference path only
+            x = x + self.attention(self.attn_norm(x), cos, sin, cache, seq=seq)
+            h = self.mlp_norm(x)
+            return x + self.w2(F.silu(self.w1(h)) * self.w3(h))
         if fused:
             from ..ops import llm
             h = llm.rmsnorm(x, self.attn_norm.weight, self.attn_norm.eps)
@@ -247,38 +290,54 @@ class Llama(nn.Module):
         return self
 
     def forward_fp8(self, tokens, cache, pos: int = 0, last_only: bool = False, tiled: bool = False,
-                    prefill_attn: bool = False, head: bool = True):
+                    prefill_attn: bool = False, head: bool = True, seq=None, last_idx=None):
         """``head=False`` (a non-final chunk of a chunked prefill): fill the
-        caches only, no final norm / LM head; returns None."""
+        caches only, no final norm / LM head; returns None.  ``seq`` = (pos_t,
+        len_t) int32 [B] device tensors: a ragged batch, one position and length
+        per sequence.  ``last_idx`` (long [B]): the head runs on token
+        last_idx[b] of sequence b and the result is [B, 1, vocab]."""
         from ..ops import llm
         cos, sin = self.rope(tokens.device)
         x = self.embed(tokens)
         for i, layer in enumerate(self.layers):
-            x = layer.forward_fp8(x, cos, sin, cache[i], pos, tiled=tiled, prefill_attn=prefill_attn)
+            x = layer.forward_fp8(x, cos, sin, cache[i], pos, tiled=tiled, prefill_attn=prefill_attn, seq=seq)
         if not head:
             return None
-        if last_only:
+        if last_idx is not None:
+            x = x[torch.arange(x.shape[0], device=x.device), last_idx].unsqueeze(1).contiguous()
+        elif last_only:
             x = x[:, -1:].contiguous()
         return llm.fp8_linear_q(*llm.rmsnorm_quant_fp8(x, self.norm.weight, self.norm.eps), self._fp8_head,
                                 tiled=tiled)
 
-    def decode_fp8_static(self, tok, cache, pos_i32, pos_i64, mask):
+    def decode_fp8_static(self, tok, cache, pos_i32, pos_i64, mask, pos_seq=None):
         from ..ops import llm
         cos, sin = self.rope(tok.device)
         x = self.embed(tok)
         for i, layer in enumerate(self.layers):
-            x = layer.decode_fp8_static(x, cos, sin, cache[i], pos_i32, pos_i64, mask)
+            x = layer.decode_fp8_static(x, cos, sin, cache[i], pos_i32, pos_i64, mask, pos_seq=pos_seq)
         return llm.fp8_linear_q(*llm.rmsnorm_quant_fp8(x, self.norm.weight, self.norm.eps), self._fp8_head)
 
     def forward(self, tokens, cache=None, pos: int = 0, fused: bool = False, last_only: bool = False,
-                prefill_attn: bool = False, head: bool = True):
+                prefill_attn: bool = False, head: bool = True, seq=None, last_idx=None):
+        """``seq`` = (pos, lens), B host ints each: a ragged batch on the eager
+        reference path (needs a cache; ``pos`` / ``fused`` are not used).
+        ``last_idx`` (long [B]): the head runs on token last_idx[b] of sequence b
+        and the result is [B, 1, vocab]."""
         cos, sin = self.rope(tokens.device)
         x = self.embed(tokens)
         for i, layer in enumerate(self.layers):
-            x = layer(x, cos, sin, None if cache is None else cache[i], pos, fused, prefill_attn)
+            if seq is not None:
+                x = layer(x, cos, sin, cache[i], seq=seq)
+            else:
+                x = layer(x, cos, sin, None if cache is None else cache[i], pos, fused, prefill_attn)
         if not head:  # a non-final chunk of a chunked prefill: the caches are filled, no logits
             return None
-        if last_only:
+        if seq is not None:
+            fused = False
+        if last_idx is not None:
+            x = x[torch.arange(x.shape[0], device=x.device), last_idx].unsqueeze(1)
+        elif last_only:
             x = x[:, -1:]
         x = self.norm(x) if not fused else __import__("pbs_amd.ops.llm", fromlist=["rmsnorm"]).rmsnorm(
             x, self.norm.weight, self.norm.eps)
@@ -303,9 +362,29 @@ class LlamaDecoder:
 
     def __init__(self, cfg: LlamaConfig, batch: int, context: int, device="cuda", dtype=torch.bfloat16,
                  fused: Optional[bool] = None, fp8: bool = False, graph: bool = False, static: bool = False,
-                 prefill_tiled: bool = False, prefill_attn: bool = False):
+                 prefill_tiled: bool = False, prefill_attn: bool = False, ragged: bool = False):
         if not 0 < context <= cfg.max_seq:  # the RoPE tables cover max_seq positions
             raise ValueError(f"LlamaDecoder: context {context} must be in [1, max_seq={cfg.max_seq}]")
+        # opt-in: every sequence of the batch has a cache position of its own
+        # (pos_b, -1 = idle slot), so prompts of different lengths share a
+        # prefill (prefill(tokens, lens=...)), a finished sequence is released
+        # and a new request admitted into its slot while the others keep
+        # decoding.  fp8=True runs the per-sequence gfx950 kernels; fp8=False is
+        # the eager reference on any device and dtype.  No sliding window.
+        G = cfg.n_heads // cfg.n_kv_heads
+        if ragged and (cfg.head_dim != 128 or cfg.n_heads % cfg.n_kv_heads or G not in (1, 2, 4, 8)):
+            raise ValueError(f"LlamaDecoder: ragged needs head_dim 128 and n_heads / n_kv_heads in 1/2/4/8, "
+                             f"got head_dim {cfg.head_dim}, {cfg.n_heads} / {cfg.n_kv_heads} heads")
+        if ragged and fused and not fp8:
+            raise ValueError("LlamaDecoder: ragged=True runs on the fp8 kernels (fp8=True) or the eager reference "
+                             "(fused=False); there is no fused bf16 ragged path")
+        self.ragged = ragged
+        if ragged:
+            prefill_attn = True  # admit() prefills at the slot's own cache position
+            if not fp8:
+                fused = False
+            else:
+                static = True  # every ragged decode step is the static-shape step
         self.cfg, self.batch, self.context = cfg, batch, context
         self.model = build(cfg, device, dtype)
         self.model.eval()
@@ -337,30 +416,128 @@ class LlamaDecoder:
                        torch.zeros(batch, cfg.n_kv_heads, context, hd, device=device, dtype=dtype))
                       for _ in range(cfg.n_layers)]
         self.pos = 0
+        # ragged state: cache position of every slot (-1 = idle); self.pos is then
+        # the largest active position, for information only
+        self.pos_b = [-1] * batch
+        self.active = [False] * batch
 
-    def _forward(self, tokens, pos: int, head: bool = True):
+    def _forward(self, tokens, pos: int, head: bool = True, cache=None, seq=None, last_idx=None):
+        """``cache``: other caches than the decoder's own (admit: the batch-1
+        views of one slot).  ``seq`` / ``last_idx``: a ragged batch, see
+        Llama.forward / forward_fp8."""
+        cache = self.cache if cache is None else cache
         if self.fp8:
-            return self.model.forward_fp8(tokens, self.cache, pos, last_only=True, tiled=self.prefill_tiled,
-                                          prefill_attn=self.prefill_attn, head=head)
-        return self.model(tokens, cache=self.cache, pos=pos, fused=self.fused, last_only=True,
-                          prefill_attn=self.prefill_attn, head=head)
+            return self.model.forward_fp8(tokens, cache, pos, last_only=True, tiled=self.prefill_tiled,
+                                          prefill_attn=self.prefill_attn, head=head, seq=seq, last_idx=last_idx)
+        return self.model(tokens, cache=cache, pos=pos, fused=self.fused, last_only=True,
+                          prefill_attn=self.prefill_attn, head=head, seq=seq, last_idx=last_idx)
+
+    @staticmethod
+    def _drain(it):
+        while True:
+            try:
+                next(it)
+            except StopIteration as e:
+                return e.value
 
     @torch.no_grad()
-    def prefill(self, tokens: torch.Tensor, chunk: Optional[int] = None) -> torch.Tensor:
+    def prefill(self, tokens: torch.Tensor, chunk: Optional[int] = None, lens=None) -> torch.Tensor:
         """Run the prompt into the KV cache and return the next token [B, 1].
         ``chunk``: run it in pieces of at most that many tokens (prefill_iter,
-        drained here); needs prefill_attn=True."""
+        drained here); needs prefill_attn=True.  ``lens`` (ragged=True): B prompt
+        lengths for tokens [B, S] padded to the longest; every slot is reset,
+        slot b becomes active with its first lens[b] tokens (0 leaves it idle),
+        in one ragged launch per layer; idle rows of the result are 0."""
+        if lens is not None:
+            if not self.ragged:
+                raise ValueError("LlamaDecoder: lens needs ragged=True")
+            if chunk is not None:
+                raise ValueError("LlamaDecoder: lens with chunk is not supported (a ragged prefill is one launch per "
+                                 "layer; admit_iter chunks one request)")
+            return self._prefill_ragged(tokens, lens)
         if chunk is not None:
-            it = self.prefill_iter(tokens, chunk)
-            while True:
-                try:
-                    next(it)
-                except StopIteration as e:
-                    return e.value
+            return self._drain(self.prefill_iter(tokens, chunk))
         self.pos = 0
         logits = self._forward(tokens, 0)
         self.pos = tokens.shape[1]
+        self._all_slots_at(self.pos)
         return logits[:, -1].argmax(-1, keepdim=True)
+
+    def _all_slots_at(self, pos: int):
+        """Ragged mode, after a uniform prefill: every slot is active at the same position."""
+        if self.ragged:
+            self.pos_b = [pos] * self.batch
+            self.active = [True] * self.batch
+
+    def _sync_pos(self):
+        self.pos = max((p for p, a in zip(self.pos_b, self.active) if a), default=0)
+
+    def _prefill_ragged(self, tokens: torch.Tensor, lens) -> torch.Tensor:
+        B, S = tokens.shape
+        lens = [int(n) for n in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
+        if B != self.batch or len(lens) != B or any(n < 0 or n > S for n in lens):
+            raise ValueError(f"LlamaDecoder: lens {lens} for tokens {tuple(tokens.shape)} and a batch of {self.batch} "
+                             f"(one length in [0, S] per slot)")
+        if max(lens) > self.context:
+            raise ValueError(f"LlamaDecoder: prompt of {max(lens)} tokens for a context of {self.context}")
+        dev = tokens.device
+        pos = [0 if n else -1 for n in lens]
+        if self.fp8:
+            seq = (torch.tensor(pos, dtype=torch.int32).to(dev), torch.tensor(lens, dtype=torch.int32).to(dev))
+        else:
+            seq = (pos, lens)
+        last = torch.tensor([max(n - 1, 0) for n in lens], device=dev)
+        self.pos_b, self.active = [-1] * B, [False] * B
+        logits = self._forward(tokens, 0, seq=seq, last_idx=last)
+        self.pos_b = [n if n else -1 for n in lens]
+        self.active = [n > 0 for n in lens]
+        self._sync_pos()
+        tok = logits[:, -1].argmax(-1, keepdim=True)
+        return tok * torch.tensor(self.active, device=dev).view(B, 1)
+
+    @torch.no_grad()
+    def admit(self, slot: int, tokens: torch.Tensor, chunk: Optional[int] = None) -> torch.Tensor:
+        """Prefill one request (tokens [S] or [1, S]) into the idle slot `slot`
+        while the other slots keep their state; returns its next token [1, 1].
+        ``chunk``: as admit_iter, drained here."""
+        n = tokens.shape[-1]
+        return self._drain(self.admit_iter(slot, tokens, n if chunk is None else chunk))
+
+    def admit_iter(self, slot: int, tokens: torch.Tensor, chunk: int):
+        """admit() as a generator over chunks of at most `chunk` tokens (the
+        uniform chunked prefill on the batch-1 views of the slot's caches): yields
+        the prompt tokens done after each chunk, so a scheduled tenant gives every
+        chunk a slice of its own and decode steps of the other slots may run in
+        between; the slot stays idle until the last chunk is done.  The next
+        token [1, 1] is the generator's return value."""
+        if not self.ragged:
+            raise ValueError("LlamaDecoder: admit needs ragged=True")
+        if not isinstance(slot, int) or isinstance(slot, bool) or not 0 <= slot < self.batch:
+            raise ValueError(f"LlamaDecoder: slot {slot!r} of a batch of {self.batch}")
+        if self.active[slot]:
+            raise ValueError(f"LlamaDecoder: slot {slot} is active (at position {self.pos_b[slot]}); release it first")
+        if not isinstance(chunk, int) or isinstance(chunk, bool) or chunk < 1:
+            raise ValueError(f"LlamaDecoder: chunk must be a positive int, got {chunk!r}")
+        tokens = tokens.view(1, -1)
+        S = tokens.shape[1]
+        if not 0 < S <= self.context:
+            raise ValueError(f"LlamaDecoder: prompt of {S} tokens for a context of {self.context}")
+        return self._admit_chunks(slot, tokens, chunk)
+
+    def _admit_chunks(self, slot: int, tokens: torch.Tensor, chunk: int):
+        # a dim-0 slice of a contiguous cache is contiguous: the uniform kernels run on it as a batch of 1
+        view = [(k[slot:slot + 1], v[slot:slot + 1]) for k, v in self.cache]
+        tok = yield from self._prefill_chunks(tokens, chunk, cache=view)
+        self.pos_b[slot], self.active[slot] = tokens.shape[1], True
+        self._sync_pos()
+        return tok
+
+    def release(self, slot: int):
+        """Mark a slot idle (its request is done); the cache rows stay as they are."""
+        if not self.ragged:
+            raise ValueError("LlamaDecoder: release needs ragged=True")
+        self.pos_b[slot], self.active[slot] = -1, False
+        self._sync_pos()
 
     def prefill_iter(self, tokens: torch.Tensor, chunk: int):
         """Chunked prefill as a generator: runs tokens[:, c : c + chunk] at cache
@@ -378,15 +555,19 @@ class LlamaDecoder:
             raise ValueError(f"LlamaDecoder: prompt of {S} tokens for a context of {self.context}")
         return self._prefill_chunks(tokens, chunk)
 
-    def _prefill_chunks(self, tokens: torch.Tensor, chunk: int):
+    def _prefill_chunks(self, tokens: torch.Tensor, chunk: int, cache=None):
+        """``cache``: the batch-1 views of one slot (admit_iter); the decoder's own
+        caches, and with them every slot, otherwise."""
         S = tokens.shape[1]
         self.pos, logits = 0, None
         for c0 in range(0, S, chunk):
             c1 = min(S, c0 + chunk)
             with torch.no_grad():
-                logits = self._forward(tokens[:, c0:c1], c0, head=(c1 == S))
+                logits = self._forward(tokens[:, c0:c1], c0, head=(c1 == S), cache=cache)
             self.pos = c1
             yield c1
+        if cache is None:
+            self._all_slots_at(S)
         return logits[:, -1].argmax(-1, keepdim=True)
 
     def _graph_setup(self, tok: torch.Tensor):
@@ -395,14 +576,21 @@ class LlamaDecoder:
         position/token uploads."""
         dev = tok.device
         self._tok = tok.clone()
-        self._pos_i32 = torch.zeros(1, dtype=torch.int32, device=dev)
-        self._pos_i64 = torch.zeros(1, dtype=torch.int64, device=dev)
-        self._ar = torch.arange(self.context, device=dev)
+        if self.ragged:  # one device position per sequence, refreshed from pos_b before every step
+            self._pos_seq = torch.full((self.batch,), -1, dtype=torch.int32, device=dev)
 
-        def step():
-            mask = torch.where(self._ar <= self._pos_i64, 0.0, float("-inf"))
-            logits = self.model.decode_fp8_static(self._tok, self.cache, self._pos_i32, self._pos_i64, mask)
-            return logits[:, -1].argmax(-1, keepdim=True)
+            def step():
+                logits = self.model.decode_fp8_static(self._tok, self.cache, None, None, None, pos_seq=self._pos_seq)
+                return logits[:, -1].argmax(-1, keepdim=True)
+        else:
+            self._pos_i32 = torch.zeros(1, dtype=torch.int32, device=dev)
+            self._pos_i64 = torch.zeros(1, dtype=torch.int64, device=dev)
+            self._ar = torch.arange(self.context, device=dev)
+
+            def step():
+                mask = torch.where(self._ar <= self._pos_i64, 0.0, float("-inf"))
+                logits = self.model.decode_fp8_static(self._tok, self.cache, self._pos_i32, self._pos_i64, mask)
+                return logits[:, -1].argmax(-1, keepdim=True)
 
         self._step = step
         if not self.graph:
@@ -419,11 +607,38 @@ class LlamaDecoder:
             self._out = step()
 
     def _set_pos(self):
+        if self.ragged:
+            self._pos_seq.copy_(torch.tensor(self.pos_b, dtype=torch.int32))
+            return
         self._pos_i32.fill_(self.pos)
         self._pos_i64.fill_(self.pos)
 
+    def _decode_step_ragged(self, tok: torch.Tensor) -> torch.Tensor:
+        for b in range(self.batch):
+            if self.active[b] and self.pos_b[b] >= self.context:
+                raise ValueError(f"LlamaDecoder: slot {b} is at position {self.pos_b[b]} = context; release it (ragged "
+                                 f"mode has no sliding window)")
+        if self.fp8:
+            if self._step is None:
+                self._graph_setup(tok)
+            self._tok.copy_(tok)
+            self._set_pos()
+            if self.graph:
+                self._g.replay()
+                out = self._out.clone()
+            else:
+                out = self._step()
+        else:
+            logits = self._forward(tok, 0, seq=(list(self.pos_b), [int(a) for a in self.active]))
+            out = logits[:, -1].argmax(-1, keepdim=True)
+        self.pos_b = [p + 1 if a else -1 for p, a in zip(self.pos_b, self.active)]
+        self._sync_pos()
+        return out
+
     @torch.no_grad()
     def decode_step(self, tok: torch.Tensor) -> torch.Tensor:
+        if self.ragged:  # advances the active slots; idle rows return a token to ignore and write nothing
+            return self._decode_step_ragged(tok)
         if self.pos >= self.context:
             self.pos = self.context // 2  # slide: keep the cache bounded for long runs
         if self.static:

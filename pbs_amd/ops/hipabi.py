@@ -92,6 +92,15 @@ def bind(lib):
        C.c_int, C.c_int, C.c_int, vp)
     _p(lib, "gpbs_hip_prefill_attn", C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
        C.c_int, C.c_float, vp)
+    # per-sequence positions (int32 [B] pos, and len for prefill) instead of one position for the batch
+    _p(lib, "gpbs_hip_qkv_rope_cache_seq", C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int,
+       C.c_int, vp)
+    _p(lib, "gpbs_hip_decode_attn_seq", C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+       C.c_int, C.c_float, vp)
+    _p(lib, "gpbs_hip_qkv_rope_cache_prefill_seq", C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int,
+       C.c_int, C.c_int, C.c_int, vp)
+    _p(lib, "gpbs_hip_prefill_attn_seq", C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+       C.c_int, C.c_float, vp)
     _p(lib, "gpbs_hip_rope_bf16", C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp)
     _p(lib, "gpbs_hip_census", C.c_int, vp, C.c_int, vp, C.c_uint, C.c_uint, vp)
     _p(lib, "gpbs_hip_partition_switch", C.c_int, vp, C.c_uint, C.POINTER(C.c_uint), vp)

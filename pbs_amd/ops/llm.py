@@ -251,6 +251,175 @@ def qkv_rope_cache_prefill(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tens
     return q
 
 
+# --------------------------------------------------------------------------- per-sequence positions (ragged batches)
+# Slot rules, applied by the kernels themselves on the device values:
+#   decode   sequence b is active iff 0 <= pos[b] < C; it writes row pos[b] and
+#            attends rows 0 .. pos[b].  Any other value is an idle slot.
+#   prefill  sequence b has n_b = min(len[b], S, C - pos[b]) new tokens at rows
+#            pos[b] .. pos[b] + n_b - 1; n_b = 0 if pos[b] < 0, pos[b] >= C or
+#            len[b] <= 0.
+# An idle slot / a padding token writes nothing to the caches and gets zero q
+# and output rows.
+def _need_seq(what: str, B: int, **vectors: torch.Tensor):
+    """The per-sequence device vectors of the _seq kernels (pos_t, len_t): each a
+    contiguous int32 [B] on the GPU.  Only the host side is checked (as
+    _need_dpos): the kernels clamp the values themselves."""
+    for name, t in vectors.items():
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 1 or t.numel() != B:
+            raise ValueError(f"{what}: {name} must be an int32 tensor of exactly B={B} elements, got "
+                             f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+        if not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be contiguous (strides {t.stride()})")
+    for name, t in vectors.items():
+        if not t.is_cuda:
+            raise ValueError(f"{what}: {name} must be a CUDA tensor (the kernel reads it), got {t.device}")
+
+
+def seq_tokens(pos: int, length: int, S: int, Cn: int) -> int:
+    """n_b of the prefill slot rule (the host twin of the kernels' clamp)."""
+    pos, length = int(pos), int(length)
+    return 0 if pos < 0 or pos >= Cn or length <= 0 else min(length, S, Cn - pos)
+
+
+def qkv_rope_cache_seq(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos_t: torch.Tensor,
+                       kc: torch.Tensor, vc: torch.Tensor, n_heads: int) -> torch.Tensor:
+    """qkv_rope_cache with one device position per sequence (pos_t int32 [B]):
+    an active sequence gets the arithmetic of qkv_rope_cache at pos_t[b]; an
+    idle one writes nothing to its caches and its q row is zero."""
+    if kc.dim() != 4 or vc.shape != kc.shape:
+        raise ValueError(f"qkv_rope_cache_seq: caches {tuple(kc.shape)} / {tuple(vc.shape)} must be [B, Hkv, C, hd] "
+                         f"of one shape")
+    B, Hkv, Cn, hd = kc.shape
+    _need_seq("qkv_rope_cache_seq", B, pos_t=pos_t)
+    _need(qkv, "qkv_rope_cache_seq qkv")
+    _need(kc, "qkv_rope_cache_seq kc")
+    _need(vc, "qkv_rope_cache_seq vc")
+    if qkv.numel() != B * (n_heads + 2 * Hkv) * hd or hd % 8 or cos.dim() != 2 or cos.shape[-1] * 2 != hd:
+        raise ValueError(f"qkv_rope_cache_seq: qkv {tuple(qkv.shape)} vs cache {tuple(kc.shape)}, H={n_heads}")
+    if cos.shape[0] < Cn or sin.shape != cos.shape or cos.dtype != torch.float32 or sin.dtype != torch.float32 \
+            or not (cos.is_cuda and sin.is_cuda and cos.is_contiguous() and sin.is_contiguous()):
+        raise ValueError(f"qkv_rope_cache_seq: rope tables {tuple(cos.shape)} {cos.dtype} must be contiguous fp32 "
+                         f"CUDA tensors covering {Cn} cache rows")
+    q = torch.empty(B, n_heads, hd, dtype=torch.bfloat16, device=qkv.device)
+    _check(lib().gpbs_hip_qkv_rope_cache_seq(_ptr(qkv), _ptr(cos), _ptr(sin), _ptr(pos_t), _ptr(q), _ptr(kc),
+                                             _ptr(vc), B, n_heads, Hkv, Cn, hd, _stream()), "qkv_rope_cache_seq")
+    return q
+
+
+def decode_attn_seq(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, pos_t: torch.Tensor,
+                    nsplit: Optional[int] = None) -> torch.Tensor:
+    """decode_attn with one device position per sequence (pos_t int32 [B]):
+    row b is bit-identical to decode_attn at pos = pos_t[b] with the same
+    nsplit; an idle sequence loads no cache row and its row is zero."""
+    if q.dim() != 3 or kc.dim() != 4 or vc.shape != kc.shape:
+        raise ValueError(f"decode_attn_seq: q {tuple(q.shape)} must be [B, H, 128], caches {tuple(kc.shape)} / "
+                         f"{tuple(vc.shape)} [B, Hkv, C, 128] of one shape")
+    B, Hkv, Cn, hd = kc.shape
+    H = q.shape[1]
+    if hd != 128 or B < 1 or Hkv < 1 or Cn < 1 or q.shape != (B, H, hd):
+        raise ValueError(f"decode_attn_seq: q {tuple(q.shape)} must be [B, H, 128] for caches {tuple(kc.shape)} "
+                         f"[B, Hkv, C, 128]")
+    if H % Hkv or (H // Hkv) not in (1, 2, 4, 8):
+        raise ValueError(f"decode_attn_seq: group size H / Hkv = {H} / {Hkv} must be 1, 2, 4 or 8")
+    for name, t in (("q", q), ("kc", kc), ("vc", vc)):
+        if t.dtype != torch.bfloat16:
+            raise ValueError(f"decode_attn_seq: {name} must be bf16, got {t.dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"decode_attn_seq: {name} must be contiguous (strides {t.stride()})")
+    if nsplit is not None and (not isinstance(nsplit, int) or isinstance(nsplit, bool) or nsplit < 1):
+        raise ValueError(f"decode_attn_seq: nsplit={nsplit!r} must be None or an int >= 1")
+    _need_seq("decode_attn_seq", B, pos_t=pos_t)
+    _need(q, "decode_attn_seq q")
+    _need(kc, "decode_attn_seq kc")
+    _need(vc, "decode_attn_seq vc")
+    out = torch.empty(B, H * hd, dtype=torch.bfloat16, device=q.device)
+    if nsplit is None:  # as decode_attn: from the shapes alone, so a row's split does not depend on its position
+        nsplit = max(1, min(8, -(-256 // (B * Hkv)), -(-Cn // 64)))
+    ws = torch.empty(B * Hkv * nsplit * (H // Hkv) * (hd + 2), dtype=torch.float32, device=q.device) \
+        if nsplit > 1 else None
+    _check(lib().gpbs_hip_decode_attn_seq(_ptr(q), _ptr(kc), _ptr(vc), _ptr(pos_t), _ptr(out), _ptr(ws), nsplit, B,
+                                          H, Hkv, Cn, hd, C.c_float(hd ** -0.5), _stream()), "decode_attn_seq")
+    return out
+
+
+def qkv_rope_cache_prefill_seq(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos_t: torch.Tensor,
+                               len_t: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor,
+                               n_heads: int) -> torch.Tensor:
+    """qkv_rope_cache_prefill with a device position and length per sequence
+    (int32 [B] each): token s < n_b of sequence b is rotated at angle row
+    pos_t[b] + s and written to that cache row; tokens s >= n_b write nothing
+    and their q rows are zero.  Returns q [B, S, H, hd]."""
+    what = "qkv_rope_cache_prefill_seq"
+    if qkv.dim() != 3 or kc.dim() != 4 or vc.shape != kc.shape:
+        raise ValueError(f"{what}: qkv {tuple(qkv.shape)} must be [B, S, (H + 2 Hkv) hd], caches "
+                         f"{tuple(kc.shape)} / {tuple(vc.shape)}")
+    B, Hkv, Cn, hd = kc.shape
+    S = qkv.shape[1]
+    if qkv.shape[0] != B or S < 1 or qkv.shape[2] != (n_heads + 2 * Hkv) * hd or hd % 8 or cos.dim() != 2 \
+            or cos.shape[-1] * 2 != hd:
+        raise ValueError(f"{what}: qkv {tuple(qkv.shape)} vs cache {tuple(kc.shape)}, H={n_heads}, "
+                         f"rope tables {tuple(cos.shape)}")
+    _need_seq(what, B, pos_t=pos_t, len_t=len_t)
+    # any row below C can be a sequence's position: the tables cover them all
+    if cos.shape[0] < Cn or sin.shape != cos.shape or cos.dtype != torch.float32 or sin.dtype != torch.float32 \
+            or not (cos.is_contiguous() and sin.is_contiguous()):
+        raise ValueError(f"{what}: rope tables {tuple(cos.shape)} {cos.dtype} must be contiguous fp32 and cover "
+                         f"C = {Cn} rows")
+    for name, t in (("qkv", qkv), ("kc", kc), ("vc", vc)):
+        if t.dtype != torch.bfloat16 or not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be contiguous bf16, got {t.dtype} strides {t.stride()}")
+    _need(qkv, f"{what} qkv")
+    _need(kc, f"{what} kc")
+    _need(vc, f"{what} vc")
+    if not (cos.is_cuda and sin.is_cuda):
+        raise ValueError(f"{what}: rope tables must be CUDA tensors")
+    q = torch.empty(B, S, n_heads, hd, dtype=torch.bfloat16, device=qkv.device)
+    _check(lib().gpbs_hip_qkv_rope_cache_prefill_seq(_ptr(qkv), _ptr(cos), _ptr(sin), _ptr(pos_t), _ptr(len_t),
+                                                     _ptr(q), _ptr(kc), _ptr(vc), B, S, n_heads, Hkv, Cn, hd,
+                                                     _stream()), what)
+    return q
+
+
+def prefill_attn_seq(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, pos_t: torch.Tensor,
+                     len_t: torch.Tensor) -> torch.Tensor:
+    """prefill_attn with a device position and length per sequence (int32 [B]
+    each): q [B, S, H, 128] padded to the longest sequence; query s < n_b of
+    sequence b attends cache rows 0 .. pos_t[b] + s and its row is bit-identical
+    to prefill_attn on that sequence alone with (S = n_b, pos = pos_t[b]).  Rows
+    s >= n_b of the result are zero, their q rows are never loaded, and no cache
+    row past pos_t[b] + n_b - 1 is addressed.  Returns [B, S, H * 128] bf16."""
+    B, S, H, Hkv, Cn, hd = _prefill_geom(q, kc, vc, 0, "prefill_attn_seq")
+    _need_seq("prefill_attn_seq", B, pos_t=pos_t, len_t=len_t)
+    _need(q, "prefill_attn_seq q")
+    _need(kc, "prefill_attn_seq kc")
+    _need(vc, "prefill_attn_seq vc")
+    out = torch.zeros(B, S, H * hd, dtype=torch.bfloat16, device=q.device)  # the kernel stores rows < n_b only
+    _check(lib().gpbs_hip_prefill_attn_seq(_ptr(q), _ptr(kc), _ptr(vc), _ptr(pos_t), _ptr(len_t), _ptr(out), B, S, H,
+                                           Hkv, Cn, hd, C.c_float(hd ** -0.5), _stream()), "prefill_attn_seq")
+    return out
+
+
+def attn_seq_ref(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, pos, lens) -> torch.Tensor:
+    """Plain-torch reference of prefill_attn_seq (and, with S = 1 and lens = 1
+    for the active slots, of decode_attn_seq); runs on the CPU.  pos / lens are
+    B ints each (lists or tensors).  prefill_attn_ref per sequence on its
+    n_b tokens, zeros for rows >= n_b; [B, S, H * hd] in the compute dtype of
+    prefill_attn_ref."""
+    B, S, H, hd = q.shape
+    Cn = kc.shape[2]
+    pos = [int(p) for p in (pos.tolist() if isinstance(pos, torch.Tensor) else pos)]
+    lens = [int(n) for n in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
+    if len(pos) != B or len(lens) != B:
+        raise ValueError(f"attn_seq_ref: {len(pos)} positions / {len(lens)} lengths for a batch of {B}")
+    ct = torch.float64 if q.dtype == torch.float64 else torch.float32
+    out = torch.zeros(B, S, H * hd, dtype=ct, device=q.device)
+    for b in range(B):
+        n = seq_tokens(pos[b], lens[b], S, Cn)
+        if n:
+            out[b, :n] = prefill_attn_ref(q[b:b + 1, :n], kc[b:b + 1], vc[b:b + 1], pos[b])[0]
+    return out
+
+
 # --------------------------------------------------------------------------- fp8 (config #5, CDNA4 fp8 MFMA)
 FP8_MAX = 448.0  # OCP e4m3fn (gfx950), not the MI300 fnuz variant
 FP8_M_TILE = 64  # rows per gpbs_hip_fp8_linear launch

@@ -8,6 +8,15 @@ last-token logits against the SDPA run.  Rounds alternate the variants in one pr
 reports the median of 5 rounds with min / max.
 
     python scripts/attn_bench.py [--iters 100] [--out prefill_attn.jsonl] [--skip-model]
+
+--ragged runs instead the per-sequence kernels against their uniform twins (B 8,
+C 8192): decode_attn_seq with every length 8192 against decode_attn at 8192,
+where decode_attn is timed twice per round so the rows carry the spread of the
+uniform kernel against itself; decode_attn_seq with lengths spread over
+1024..8192; prefill_attn_seq with lengths 1024, 512, 256, 64 (twice) against
+prefill_attn at S 1024.
+
+    python scripts/attn_bench.py --ragged [--iters 100] [--out profiles/ragged_attn.jsonl]
 """
 import argparse
 import json
@@ -145,12 +154,60 @@ def model_rows(emit, batch, prompt, rounds):
           "min_cos_logits": cmin, "mean_cos_logits": cmean})
 
 
+def ragged_rows(emit, g, iters, B=8, C=8192):
+    i32 = dict(dtype=torch.int32, device="cuda")
+    q = torch.randn(B, H, HD, device="cuda", generator=g).bfloat16()
+    kc = torch.randn(B, HKV, C, HD, device="cuda", generator=g).bfloat16()
+    vc = torch.randn(B, HKV, C, HD, device="cuda", generator=g).bfloat16()
+    pos1 = torch.tensor([C - 1], **i32)
+    full = torch.full((B,), C - 1, **i32)
+    spread_l = [1024 + (C - 1024) * b // (B - 1) for b in range(B)]
+    spread = torch.tensor([n - 1 for n in spread_l], **i32)
+    S = 1024
+    qp = torch.randn(B, S, H, HD, device="cuda", generator=g).bfloat16()
+    lens_l = [1024, 512, 256, 64] * (B // 4)
+    zeros, lens, all_s = torch.zeros(B, **i32), torch.tensor(lens_l, **i32), torch.full((B,), S, **i32)
+    variants = {
+        "decode_attn@8192 (first)": lambda: llm.decode_attn(q, kc, vc, pos1),
+        "decode_attn_seq all 8192": lambda: llm.decode_attn_seq(q, kc, vc, full),
+        "decode_attn@8192 (second)": lambda: llm.decode_attn(q, kc, vc, pos1),
+        "decode_attn_seq 1024..8192": lambda: llm.decode_attn_seq(q, kc, vc, spread),
+        "prefill_attn S 1024": lambda: llm.prefill_attn(qp, kc, vc, 0),
+        "prefill_attn_seq all 1024": lambda: llm.prefill_attn_seq(qp, kc, vc, zeros, all_s),
+        "prefill_attn_seq 1024/512/256/64": lambda: llm.prefill_attn_seq(qp, kc, vc, zeros, lens),
+    }
+    assert torch.equal(variants["decode_attn_seq all 8192"](), variants["decode_attn@8192 (first)"]())
+    assert torch.equal(variants["prefill_attn_seq all 1024"](), variants["prefill_attn S 1024"]())
+    times = {k: [] for k in variants}
+    for _ in range(ROUNDS):  # the variants alternate within a round
+        for k, fn in variants.items():
+            times[k].append(timeit(fn, iters))
+    m = {k: med(v) for k, v in times.items()}
+    base = {"decode_attn@8192 (second)": "decode_attn@8192 (first)",
+            "decode_attn_seq all 8192": "decode_attn@8192 (first)",
+            "decode_attn_seq 1024..8192": "decode_attn_seq all 8192",
+            "prefill_attn_seq all 1024": "prefill_attn S 1024",
+            "prefill_attn_seq 1024/512/256/64": "prefill_attn S 1024"}
+    info = {"decode_attn_seq 1024..8192": {"lengths": spread_l, "keys_over_full": round(sum(spread_l) / (B * C), 3)},
+            "prefill_attn_seq 1024/512/256/64": {
+                "lengths": lens_l,
+                "work_over_full": round(sum(n * (n + 1) for n in lens_l) / (B * S * (S + 1)), 3)}}
+    for k in variants:
+        rec = {"bench": "ragged_attn", "name": k, "B": B, "C": C, "H": H, "Hkv": HKV, "us": round(m[k], 1),
+               "us_minmax": [round(min(times[k]), 1), round(max(times[k]), 1)]}
+        if k in base:
+            rec.update({"over": base[k], "ratio": round(m[k] / m[base[k]], 3)})
+        rec.update(info.get(k, {}))
+        emit(rec)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--out", default="")
     ap.add_argument("--skip-model", action="store_true")
     ap.add_argument("--skip-kernel", action="store_true")
+    ap.add_argument("--ragged", action="store_true", help="only the per-sequence kernels against their uniform twins")
     a = ap.parse_args()
     out = open(a.out, "a") if a.out else None
 
@@ -161,6 +218,9 @@ def main():
             out.flush()
 
     g = torch.Generator(device="cuda").manual_seed(0)
+    if a.ragged:
+        ragged_rows(emit, g, a.iters)
+        return
     if not a.skip_kernel:
         kernel_row(emit, g, a.iters, 8, 1024, 0, 2048, "llm5 prompt")
         t0 = kernel_row(emit, g, a.iters, 1, 4096, 0, 8192, "4k prompt")
