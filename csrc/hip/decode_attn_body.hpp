@@ -1,11 +1,20 @@
 // The decode attention kernel and its combine kernel.  Not a header of its own:
-// decode_kernels.hip includes this text twice, inside namespace gpbs_dec, with
+// decode_kernels.hip includes this text three times, inside namespace gpbs_dec, with
 // GPBS_SEQ 0 (k_decode_attn, k_decode_attn_combine: one device position for
 // the batch) and GPBS_SEQ 1 (k_decode_attn_seq, k_decode_attn_combine_seq: dpos
 // is int32 [B]; sequence b has L = dpos[b] + 1 keys if 0 <= dpos[b] < C and is
 // idle otherwise: L = 0, no key loop, zero output).  Everything outside the
 // #if blocks is shared, so an active sequence gets the uniform kernel's bits.
-#if GPBS_SEQ
+// GPBS_SEQ 2 is a third compilation, k_decode_attn_paged: the _seq kernel over
+// pools [P, Hkv, page, 128] addressed through an int32 block table [B, NP]
+// (logical row r of sequence b: page table[b, r / page], page row r % page;
+// Cl = NP * page stands where C stood).  A 64-key step never straddles a page,
+// so the only new work is one wave-uniform table entry per step, loaded one
+// step ahead; an entry outside [0, P) reads page 0.  It emits no combine
+// kernel: k_decode_attn_combine_seq touches no cache and serves it as it is.
+#if GPBS_SEQ == 2
+#define GPBS_DEC_ATTN k_decode_attn_paged
+#elif GPBS_SEQ
 #define GPBS_DEC_ATTN k_decode_attn_seq
 #define GPBS_DEC_COMBINE k_decode_attn_combine_seq
 #else
@@ -18,9 +27,17 @@ template <int G>
 __global__ __launch_bounds__(kAttnWaves * 64) void GPBS_DEC_ATTN(const u32x4* __restrict__ q,
                                                                const u32x4* __restrict__ kc,
                                                                const u32* __restrict__ vc,
+#if GPBS_SEQ == 2
+                                                               const int* __restrict__ dpos,
+                                                               const int* __restrict__ table, u32* __restrict__ out,
+                                                               float* __restrict__ ws, int Hkv, int NP, int P, int psh,
+                                                               float scale, int nsplit) {
+  const int C = NP << psh;  // the logical context Cl
+#else
                                                                const int* __restrict__ dpos, u32* __restrict__ out,
                                                                float* __restrict__ ws, int Hkv, int C, float scale,
                                                                int nsplit) {
+#endif
   __shared__ float qs[G][kHd];
   __shared__ float ms[kAttnWaves][G], ls[kAttnWaves][G];
   __shared__ float os[kAttnWaves][G][kHd];
@@ -48,9 +65,18 @@ __global__ __launch_bounds__(kAttnWaves * 64) void GPBS_DEC_ATTN(const u32x4* __
     }
   }
   __syncthreads();
+#if GPBS_SEQ == 2
+  // the bases of KV head kvh in page 0; a page is Hkv << psh rows further on
+  const u32x4* kh = kc + ((size_t)kvh << psh) * (kHd / 8);
+  const u32* vh = vc + ((size_t)kvh << psh) * (kHd / 2);
+  const int* trow = table + (size_t)b * NP;
+  const int base0 = __builtin_amdgcn_readfirstlane(k0 + w * 64);
+  int pg = base0 < k1 ? page_or0(trow[base0 >> psh], P) : 0;  // the page of this wave's first step
+#else
   const size_t head = (size_t)b * Hkv + kvh;
   const u32x4* kh = kc + head * C * (kHd / 8);
   const u32* vh = vc + head * C * (kHd / 2);
+#endif
   // PV lane map: key group kg = lane >> 4 takes keys kg, kg + 4, ...; dl = lane & 15
   // owns dims 8 dl .. 8 dl + 7 (one 16-byte V load per key)
   const int kg = lane >> 4, dl = lane & 15;
@@ -62,7 +88,15 @@ __global__ __launch_bounds__(kAttnWaves * 64) void GPBS_DEC_ATTN(const u32x4* __
     for (int e = 0; e < 8; ++e) o[g][e] = 0.f;
   }
 
+#if GPBS_SEQ == 2
+  for (int base = base0; base < k1; base += kAttnWaves * 64) {
+    // rows of this step within the pools: page pg, page rows base % page ..; the
+    // next step's entry (only if that step has keys) is in flight under this one
+    const size_t prow = ((size_t)pg * Hkv << psh) + (base & ((1 << psh) - 1));
+    if (base + kAttnWaves * 64 < k1) pg = page_or0(trow[(base + kAttnWaves * 64) >> psh], P);
+#else
   for (int base = k0 + w * 64; base < k1; base += kAttnWaves * 64) {
+#endif
     const int j = base + lane;
     float s[G];
 #pragma unroll
@@ -73,7 +107,11 @@ __global__ __launch_bounds__(kAttnWaves * 64) void GPBS_DEC_ATTN(const u32x4* __
     asm volatile("" : "+s"(z));
     const float* qz = &qs[0][0] + z;
     if (j < k1) {
+#if GPBS_SEQ == 2
+      const u32x4* kr = kh + (prow + lane) * (kHd / 8);
+#else
       const u32x4* kr = kh + (size_t)j * (kHd / 8);
+#endif
       u32x4 krow[kHd / 8];  // the lane's whole 256-byte key row in flight at once
 #pragma unroll
       for (int c = 0; c < kHd / 8; ++c) krow[c] = kr[c];
@@ -102,7 +140,11 @@ __global__ __launch_bounds__(kAttnWaves * 64) void GPBS_DEC_ATTN(const u32x4* __
       m[g] = mn;
     }
     // PV: 16 rounds of 4 keys (one per key group), 16-byte V loads, weights by shuffle
+#if GPBS_SEQ == 2
+    const u32x4* vb = reinterpret_cast<const u32x4*>(vh) + prow * (kHd / 8) + dl;
+#else
     const u32x4* vb = reinterpret_cast<const u32x4*>(vh) + (size_t)base * (kHd / 8) + dl;
+#endif
 #pragma unroll 4
     for (int t = 0; t < 16; ++t) {
       const int jj = 4 * t + kg;
@@ -168,6 +210,7 @@ __global__ __launch_bounds__(kAttnWaves * 64) void GPBS_DEC_ATTN(const u32x4* __
   }
 }
 
+#if GPBS_SEQ != 2
 // Merge the nsplit partials of each (batch, KV head): grid B * Hkv, G * 64 threads.
 __global__ __launch_bounds__(512) void GPBS_DEC_COMBINE(const float* __restrict__ ws, u32* __restrict__ out,
                                                              int Hkv, int G, int nsplit) {
@@ -191,6 +234,7 @@ __global__ __launch_bounds__(512) void GPBS_DEC_COMBINE(const float* __restrict_
 #endif
   out[((size_t)b * Hkv * G + kvh * G + g) * (kHd / 2) + d / 2] = pack2(a0 * inv, a1 * inv);
 }
+#endif
 
 #undef GPBS_DEC_ATTN
 #undef GPBS_DEC_COMBINE

@@ -20,7 +20,16 @@
 // idle slot.  An idle sequence writes no cache row, loads none, and its q / out
 // rows are zero bits; an active one computes exactly what the uniform kernel
 // computes at pos = pos[b] (same chunking, same order of operations).
+//
+// The _paged forms are the _seq forms over a paged cache: pools
+// [P, Hkv, page, hd] and an int32 block table [B, NP]; logical row r of sequence
+// b lives in page table[b, r / page] at page row r % page, page in 64/128/256,
+// and Cl = NP * page takes the place of C in the slot rule.  Only the entries
+// of pages that hold rows 0 .. pos[b] are read.  An entry outside [0, P) never
+// forms an address outside the pools: the write through it is dropped, the
+// reads through it come from page 0.
 #include <algorithm>
+#include <climits>
 
 #include "common.hpp"
 
@@ -104,6 +113,53 @@ __global__ __launch_bounds__(256) void k_qkv_rope_cache_seq(const u32x4* __restr
   }
 }
 
+// a block-table entry as a page to read: anything outside [0, P) is page 0
+__device__ __forceinline__ int page_or0(int e, int P) { return (e >= 0 && e < P) ? e : 0; }
+
+// k_qkv_rope_cache_seq through the block table: an active sequence (0 <= pos[b] <
+// NP * page) writes row pos[b] % page of page table[b, pos[b] / page]; the write
+// is dropped if that entry is outside [0, P).
+__global__ __launch_bounds__(256) void k_qkv_rope_cache_paged(const u32x4* __restrict__ qkv,
+                                                              const float* __restrict__ cosb,
+                                                              const float* __restrict__ sinb,
+                                                              const int* __restrict__ posb,
+                                                              const int* __restrict__ table, u32x4* __restrict__ qo,
+                                                              u32x4* __restrict__ kp, u32x4* __restrict__ vp, int B,
+                                                              int H, int Hkv, int NP, int P, int psh, int hd) {
+  const int per_head = hd / 8, heads = H + 2 * Hkv;
+  const size_t n8 = (size_t)B * heads * per_head;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (size_t)gridDim.x * blockDim.x) {
+    const int c = (int)(i % per_head);
+    const int hh = (int)((i / per_head) % heads);
+    const int b = (int)(i / per_head / heads);
+    const int pos = posb[b];
+    if (pos < 0 || pos >= (NP << psh)) {  // idle slot
+      if (hh < H) qo[((size_t)b * H + hh) * per_head + c] = u32x4{0u, 0u, 0u, 0u};
+      continue;
+    }
+    const u32x4 v = qkv[i];
+    const int pg = table[(size_t)b * NP + (pos >> psh)];
+    const bool ok = pg >= 0 && pg < P;
+    const int prow = pos & ((1 << psh) - 1);
+    if (hh >= H + Hkv) {  // v: plain copy into the page row
+      if (ok) vp[((((size_t)pg * Hkv + (hh - H - Hkv)) << psh) + prow) * per_head + c] = v;
+      continue;
+    }
+    const float* cr = cosb + (size_t)pos * (hd / 2) + c * 4;
+    const float* sr = sinb + (size_t)pos * (hd / 2) + c * 4;
+    u32x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float a = bfl(v[e]), bb = bfh(v[e]), cs = cr[e], sn = sr[e];
+      o[e] = pack2(a * cs - bb * sn, a * sn + bb * cs);
+    }
+    if (hh < H)
+      qo[((size_t)b * H + hh) * per_head + c] = o;
+    else if (ok)
+      kp[((((size_t)pg * Hkv + (hh - H)) << psh) + prow) * per_head + c] = o;
+  }
+}
+
 constexpr int kHd = 128;  // head_dim of every Llama-3 size
 constexpr int kAttnWaves = 8;
 
@@ -125,6 +181,10 @@ __device__ __forceinline__ float wsum(float v) {
 #include "decode_attn_body.hpp"
 #undef GPBS_SEQ
 #define GPBS_SEQ 1
+#include "decode_attn_body.hpp"
+#undef GPBS_SEQ
+// third compilation: k_decode_attn_paged<G> (merged by k_decode_attn_combine_seq)
+#define GPBS_SEQ 2
 #include "decode_attn_body.hpp"
 #undef GPBS_SEQ
 
@@ -194,6 +254,50 @@ int gpbs_hip_decode_attn_seq(const void* q, const void* kc, const void* vc, cons
     default: return -22;
   }
 #undef GPBS_DEC_SEQ_LAUNCH
+  if (nsplit > 1)
+    hipLaunchKernelGGL(k_decode_attn_combine_seq, dim3(B * Hkv), dim3(G * 64), 0, s, (const float*)w, (u32*)out, Hkv,
+                       G, nsplit);
+  return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+// log2(page) for the page sizes the paged kernels take, -1 otherwise
+static int page_shift(int page) { return page == 64 ? 6 : page == 128 ? 7 : page == 256 ? 8 : -1; }
+
+int gpbs_hip_qkv_rope_cache_paged(const void* qkv, const float* cosb, const float* sinb, const int* posb,
+                                  const int* table, void* qo, void* kp, void* vp, int B, int H, int Hkv, int NP, int P,
+                                  int page, int hd, hipStream_t s) {
+  const int psh = page_shift(page);
+  if (B <= 0 || H <= 0 || Hkv <= 0 || NP < 1 || P < 1 || psh < 0 || hd != kHd || !posb || !table ||
+      ((long long)NP << psh) > INT_MAX)
+    return -22;
+  const size_t n8 = (size_t)B * (H + 2 * Hkv) * hd / 8;
+  int grid = (int)std::min<size_t>((n8 + 255) / 256, 2048);
+  hipLaunchKernelGGL(k_qkv_rope_cache_paged, dim3(grid), dim3(256), 0, s, (const u32x4*)qkv, cosb, sinb, posb, table,
+                     (u32x4*)qo, (u32x4*)kp, (u32x4*)vp, B, H, Hkv, NP, P, psh, hd);
+  return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+int gpbs_hip_decode_attn_paged(const void* q, const void* kp, const void* vp, const int* posb, const int* table,
+                               void* out, void* ws, int nsplit, int B, int H, int Hkv, int NP, int P, int page, int hd,
+                               float scale, hipStream_t s) {
+  const int psh = page_shift(page);
+  if (hd != kHd || B <= 0 || Hkv <= 0 || H % Hkv || NP < 1 || P < 1 || psh < 0 || !posb || !table || nsplit < 1 ||
+      (nsplit > 1 && !ws) || ((long long)NP << psh) > INT_MAX)
+    return -22;
+  const int G = H / Hkv;
+  const dim3 grid(B * Hkv * nsplit), block(kAttnWaves * 64);
+  float* w = (float*)ws;
+#define GPBS_DEC_PAGED_LAUNCH(g)                                                                                   \
+  hipLaunchKernelGGL(k_decode_attn_paged<g>, grid, block, 0, s, (const u32x4*)q, (const u32x4*)kp, (const u32*)vp, \
+                     posb, table, (u32*)out, w, Hkv, NP, P, psh, scale, nsplit)
+  switch (G) {
+    case 1: GPBS_DEC_PAGED_LAUNCH(1); break;
+    case 2: GPBS_DEC_PAGED_LAUNCH(2); break;
+    case 4: GPBS_DEC_PAGED_LAUNCH(4); break;
+    case 8: GPBS_DEC_PAGED_LAUNCH(8); break;
+    default: return -22;
+  }
+#undef GPBS_DEC_PAGED_LAUNCH
   if (nsplit > 1)
     hipLaunchKernelGGL(k_decode_attn_combine_seq, dim3(B * Hkv), dim3(G * 64), 0, s, (const float*)w, (u32*)out, Hkv,
                        G, nsplit);

@@ -1,5 +1,5 @@
 // The prefill attention kernel.  Not a header of its own: prefill_kernels.hip
-// includes this text twice, inside namespace gpbs_pf, with GPBS_SEQ 0
+// includes this text three times, inside namespace gpbs_pf, with GPBS_SEQ 0
 // (k_prefill_attn: S and pos are kernel arguments) and GPBS_SEQ 1
 // (k_prefill_attn_seq: the launch is sized for Sq tokens per sequence, the row
 // stride of q / out, and a workgroup takes pos = posb[b] and S = n_b, the tokens
@@ -7,6 +7,14 @@
 // blocks is shared: tiles, diagonal and clamps follow the workgroup's own
 // (S, pos), so sequence b gets the bits of the uniform kernel run on it alone.
 // Rows s >= n_b of out are not stored: the caller hands in a zeroed out.
+// GPBS_SEQ 2 is a third compilation, k_prefill_attn_paged: the _seq kernel over
+// pools [P, Hkv, page, 128] addressed through an int32 block table [B, NP]
+// (logical row r of sequence b: page table[b, r / page], page row r % page;
+// Cl = NP * page stands where C stood).  A staged tile of kKT rows never
+// straddles a page, and the krow_last clamp stays inside the tile that holds
+// krow_last, so the only new work is one workgroup-uniform table entry per
+// tile, loaded one prefetch ahead of the rows it addresses; an entry outside
+// [0, P) reads page 0.
 #if GPBS_SEQ
 #define GPBS_PF_STRIDE Sq
 #else
@@ -15,7 +23,17 @@
 
 // q [B, S, H, 128], caches [B, Hkv, C, 128], out [B, S, H * 128]; H = G * Hkv.
 template <int G>
-#if GPBS_SEQ
+#if GPBS_SEQ == 2
+__global__ __launch_bounds__(kWaves * 64) void k_prefill_attn_paged(const u32x4* __restrict__ q,
+                                                                    const u32x4* __restrict__ kc,
+                                                                    const u32x4* __restrict__ vc,
+                                                                    const int* __restrict__ posb,
+                                                                    const int* __restrict__ lenb,
+                                                                    const int* __restrict__ table,
+                                                                    u32x2* __restrict__ out, int Sq, int Hkv, int NP,
+                                                                    int P, int psh, float scale_log2e, int nbh) {
+  const int C = NP << psh;  // the logical context Cl
+#elif GPBS_SEQ
 __global__ __launch_bounds__(kWaves * 64) void k_prefill_attn_seq(const u32x4* __restrict__ q,
                                                                   const u32x4* __restrict__ kc,
                                                                   const u32x4* __restrict__ vc,
@@ -62,11 +80,26 @@ __global__ __launch_bounds__(kWaves * 64) void k_prefill_attn(const u32x4* __res
 
   // staging: piece i of this thread is chunk sch of tile row srow + 32 i
   const int srow = tid >> 4, sch = tid & 15;
+#if GPBS_SEQ == 2
+  // row r of tile t sits in page table[b, t kKT / page] at page row r % page;
+  // pgn is the entry of the tile the next prefetch loads, fetched one tile ahead
+  const int* trow = table + (size_t)b * NP;
+  const int pmask = (1 << psh) - 1;
+  const size_t head = (size_t)kvh << psh;
+  const size_t pstride = (size_t)Hkv << psh;
+  const int pg0 = page_or0(trow[0], P);
+  int pgn = ntiles > 1 ? page_or0(trow[kKT >> psh], P) : 0;
+#else
   const size_t head = ((size_t)b * Hkv + kvh) * C;
+#endif
   u32x4 kr[2], vr[2];
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
+#if GPBS_SEQ == 2
+    const size_t row = head + pg0 * pstride + min(srow + 32 * i, krow_last);  // tile 0: page row == row
+#else
     const size_t row = head + min(srow + 32 * i, krow_last);
+#endif
     kr[i] = kc[row * (kHd / 8) + sch];
     vr[i] = vc[row * (kHd / 8) + sch];
   }
@@ -100,9 +133,17 @@ __global__ __launch_bounds__(kWaves * 64) void k_prefill_attn(const u32x4* __res
     }
     __syncthreads();
     if (t + 1 < ntiles) {  // next tile in flight under this tile's MFMAs
+#if GPBS_SEQ == 2
+      const size_t pbase = head + pgn * pstride;
+      if (t + 2 < ntiles) pgn = page_or0(trow[((t + 2) * kKT) >> psh], P);
+#endif
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
+#if GPBS_SEQ == 2
+        const size_t row = pbase + (min((t + 1) * kKT + srow + 32 * i, krow_last) & pmask);
+#else
         const size_t row = head + min((t + 1) * kKT + srow + 32 * i, krow_last);
+#endif
         kr[i] = kc[row * (kHd / 8) + sch];
         vr[i] = vc[row * (kHd / 8) + sch];
       }

@@ -56,6 +56,14 @@
 // pos[b] + n_b - 1 is addressed.  The tile walk of a workgroup depends on its
 // sequence alone, so sequence b gets the bits of the uniform kernel run on it
 // alone with (S = n_b, pos = pos[b]).
+//
+// The _paged forms are the _seq forms over a paged cache: pools
+// [P, Hkv, page, hd] and an int32 block table [B, NP]; logical row r of sequence
+// b lives in page table[b, r / page] at page row r % page, page in 64/128/256,
+// and Cl = NP * page takes the place of C in n_b.  Only the entries of pages
+// that hold rows 0 .. pos[b] + n_b - 1 are read.  An entry outside [0, P) never
+// forms an address outside the pools: writes through it are dropped, reads
+// through it come from page 0.
 #include <algorithm>
 #include <climits>
 
@@ -149,6 +157,57 @@ __global__ __launch_bounds__(256) void k_qkv_rope_cache_prefill_seq(const u32x4*
   }
 }
 
+// a block-table entry as a page to read: anything outside [0, P) is page 0
+__device__ __forceinline__ int page_or0(int e, int P) { return (e >= 0 && e < P) ? e : 0; }
+
+// k_qkv_rope_cache_prefill_seq through the block table: token s < n_b of sequence
+// b goes to row (pos[b] + s) % page of page table[b, (pos[b] + s) / page]; the
+// write is dropped if that entry is outside [0, P).
+__global__ __launch_bounds__(256) void k_qkv_rope_cache_prefill_paged(const u32x4* __restrict__ qkv,
+                                                                      const float* __restrict__ cosb,
+                                                                      const float* __restrict__ sinb,
+                                                                      const int* __restrict__ posb,
+                                                                      const int* __restrict__ lenb,
+                                                                      const int* __restrict__ table,
+                                                                      u32x4* __restrict__ qo, u32x4* __restrict__ kp,
+                                                                      u32x4* __restrict__ vp, int B, int S, int H,
+                                                                      int Hkv, int NP, int P, int psh, int hd) {
+  const int per_head = hd / 8, heads = H + 2 * Hkv;
+  const size_t n8 = (size_t)B * S * heads * per_head;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (size_t)gridDim.x * blockDim.x) {
+    const int c = (int)(i % per_head);
+    const int hh = (int)((i / per_head) % heads);
+    const size_t bs = i / per_head / heads;
+    const int s = (int)(bs % S), b = (int)(bs / S);
+    const int pos = posb[b];
+    if (s >= seq_tokens(pos, lenb[b], S, NP << psh)) {  // padding token
+      if (hh < H) qo[(bs * H + hh) * per_head + c] = u32x4{0u, 0u, 0u, 0u};
+      continue;
+    }
+    const u32x4 v = qkv[i];
+    const int r = pos + s;
+    const int pg = table[(size_t)b * NP + (r >> psh)];
+    const bool ok = pg >= 0 && pg < P;
+    const int prow = r & ((1 << psh) - 1);
+    if (hh >= H + Hkv) {  // v: plain copy into the page row
+      if (ok) vp[((((size_t)pg * Hkv + (hh - H - Hkv)) << psh) + prow) * per_head + c] = v;
+      continue;
+    }
+    const float* cr = cosb + (size_t)r * (hd / 2) + c * 4;
+    const float* sr = sinb + (size_t)r * (hd / 2) + c * 4;
+    u32x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float a = bfl(v[e]), bb = bfh(v[e]), cs = cr[e], sn = sr[e];
+      o[e] = pack2(a * cs - bb * sn, a * sn + bb * cs);
+    }
+    if (hh < H)
+      qo[(bs * H + hh) * per_head + c] = o;
+    else if (ok)
+      kp[((((size_t)pg * Hkv + (hh - H)) << psh) + prow) * per_head + c] = o;
+  }
+}
+
 constexpr int kHd = 128;
 constexpr int kWaves = 8;
 constexpr int kRows = kWaves * 32;  // query rows (token x head of the group) per workgroup
@@ -171,6 +230,10 @@ __device__ __forceinline__ float ex2(float x) { return __builtin_amdgcn_exp2f(x)
 #include "prefill_attn_body.hpp"
 #undef GPBS_SEQ
 #define GPBS_SEQ 1
+#include "prefill_attn_body.hpp"
+#undef GPBS_SEQ
+// third compilation: k_prefill_attn_paged<G>
+#define GPBS_SEQ 2
 #include "prefill_attn_body.hpp"
 #undef GPBS_SEQ
 
@@ -253,6 +316,51 @@ int gpbs_hip_prefill_attn_seq(const void* q, const void* kc, const void* vc, con
     default: GPBS_PF_SEQ_LAUNCH(8); break;
   }
 #undef GPBS_PF_SEQ_LAUNCH
+  return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+// log2(page) for the page sizes the paged kernels take, -1 otherwise
+static int page_shift(int page) { return page == 64 ? 6 : page == 128 ? 7 : page == 256 ? 8 : -1; }
+
+int gpbs_hip_qkv_rope_cache_prefill_paged(const void* qkv, const float* cosb, const float* sinb, const int* posb,
+                                          const int* lenb, const int* table, void* qo, void* kp, void* vp, int B,
+                                          int S, int H, int Hkv, int NP, int P, int page, int hd, hipStream_t s) {
+  const int psh = page_shift(page);
+  if (!qkv || !cosb || !sinb || !posb || !lenb || !table || !qo || !kp || !vp || B <= 0 || S <= 0 || H <= 0 ||
+      Hkv <= 0 || NP < 1 || P < 1 || psh < 0 || hd != kHd || ((long long)NP << psh) > INT_MAX)
+    return -22;
+  const size_t n8 = (size_t)B * S * (H + 2 * Hkv) * hd / 8;
+  const int grid = (int)std::min<size_t>((n8 + 255) / 256, 8192);
+  hipLaunchKernelGGL(k_qkv_rope_cache_prefill_paged, dim3(grid), dim3(256), 0, s, (const u32x4*)qkv, cosb, sinb, posb,
+                     lenb, table, (u32x4*)qo, (u32x4*)kp, (u32x4*)vp, B, S, H, Hkv, NP, P, psh, hd);
+  return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+// out must come in zeroed: rows s >= n_b are left as they are
+int gpbs_hip_prefill_attn_paged(const void* q, const void* kp, const void* vp, const int* posb, const int* lenb,
+                                const int* table, void* out, int B, int S, int H, int Hkv, int NP, int P, int page,
+                                int hd, float scale, hipStream_t s) {
+  const int psh = page_shift(page);
+  if (!q || !kp || !vp || !posb || !lenb || !table || !out || hd != kHd || B <= 0 || S <= 0 || H <= 0 || Hkv <= 0 ||
+      H % Hkv || NP < 1 || P < 1 || psh < 0 || ((long long)NP << psh) > INT_MAX)
+    return -22;
+  const int G = H / Hkv;
+  if (G != 1 && G != 2 && G != 4 && G != 8) return -22;
+  const int tpw = kRows / G;
+  const long long nwg = (long long)((S + tpw - 1) / tpw) * B * Hkv;
+  if (nwg > INT_MAX) return -22;
+  const dim3 grid((unsigned)nwg), block(kWaves * 64);
+  const float sl = scale * 1.44269504088896340736f;
+#define GPBS_PF_PAGED_LAUNCH(g)                                                                                        \
+  hipLaunchKernelGGL(k_prefill_attn_paged<g>, grid, block, 0, s, (const u32x4*)q, (const u32x4*)kp, (const u32x4*)vp, \
+                     posb, lenb, table, (u32x2*)out, S, Hkv, NP, P, psh, sl, B * Hkv)
+  switch (G) {
+    case 1: GPBS_PF_PAGED_LAUNCH(1); break;
+    case 2: GPBS_PF_PAGED_LAUNCH(2); break;
+    case 4: GPBS_PF_PAGED_LAUNCH(4); break;
+    default: GPBS_PF_PAGED_LAUNCH(8); break;
+  }
+#undef GPBS_PF_PAGED_LAUNCH
   return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 

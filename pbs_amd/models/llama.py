@@ -25,6 +25,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .paging import PagePool, PoolExhausted  # noqa: F401  (PoolExhausted is part of the decoder's interface)
+
 
 @dataclass
 class LlamaConfig:
@@ -165,7 +167,8 @@ class Block(nn.Module):
             "w2": llm.Fp8Weight(self.w2.weight),
         }
 
-    def forward_fp8(self, x, cos, sin, cache, pos: int, tiled: bool = False, prefill_attn: bool = False, seq=None):
+    def forward_fp8(self, x, cos, sin, cache, pos: int, tiled: bool = False, prefill_attn: bool = False, seq=None,
+                    table=None):
         """Decode/prefill block on fp8 weights (fp8 MFMA linears + fused gfx950
         RMSNorm/RoPE/SwiGLU); inference only.  ``tiled``: the linears run the
         LDS-tiled fp8 GEMM (one launch for any M) where their N allows it.
@@ -173,7 +176,9 @@ class Block(nn.Module):
         (qkv_rope_cache_prefill, prefill_attn) instead of RoPE, cache copies and
         SDPA.  ``seq`` = (pos_t, len_t), int32 [B] device tensors: the ragged
         form of those two launches, one position and length per sequence (any
-        S; ``pos`` is not used)."""
+        S; ``pos`` is not used).  ``table`` (with ``seq``): int32 [B, NP] block
+        table on the device; ``cache`` is then the layer's (kpool, vpool) and the
+        two launches are the paged kernels."""
         from ..ops import llm
         cfg, hd, f = self.cfg, self.cfg.head_dim, self._fp8
         B, S, _ = x.shape
@@ -181,7 +186,10 @@ class Block(nn.Module):
                                tiled=tiled)
         nq, nkv = cfg.n_heads * hd, cfg.n_kv_heads * hd
         kc, vc = cache
-        if seq is not None:
+        if seq is not None and table is not None:
+            q = llm.qkv_rope_cache_prefill_paged(qkv, cos, sin, seq[0], seq[1], table, kc, vc, cfg.n_heads)
+            o = llm.prefill_attn_paged(q, kc, vc, table, seq[0], seq[1])
+        elif seq is not None:
             q = llm.qkv_rope_cache_prefill_seq(qkv, cos, sin, seq[0], seq[1], kc, vc, cfg.n_heads)
             o = llm.prefill_attn_seq(q, kc, vc, seq[0], seq[1])
         elif prefill_attn and S > 1:
@@ -202,13 +210,15 @@ class Block(nn.Module):
                               tiled=tiled)
         return x + llm.fp8_linear_q(*llm.swiglu_quant_fp8(gu), f["w2"], tiled=tiled)
 
-    def decode_fp8_static(self, x, cos, sin, cache, pos_i32, pos_i64, mask, pos_seq=None):
+    def decode_fp8_static(self, x, cos, sin, cache, pos_i32, pos_i64, mask, pos_seq=None, table=None):
         """One-token decode with every shape static and the position on device
         (capturable in a HIP graph): the KV row is written with index_copy_ at
         pos, and attention runs over the whole static cache with an additive
         mask, grouped per KV head (GQA without repeating K/V).  ``pos_seq``
         (int32 [B] on device, head_dim 128 only): one position per sequence,
-        idle slots write nothing; pos_i32 / pos_i64 / mask are not used."""
+        idle slots write nothing; pos_i32 / pos_i64 / mask are not used.
+        ``table`` (with ``pos_seq``): int32 [B, NP] block table on the device;
+        ``cache`` is then the layer's (kpool, vpool) and the paged kernels run."""
         from ..ops import llm
         cfg, hd, f = self.cfg, self.cfg.head_dim, self._fp8
         B = x.shape[0]
@@ -218,7 +228,10 @@ class Block(nn.Module):
         kc, vc = cache
         # fused gfx950 path: 2 launches between the qkv and o linears
         if pos_seq is not None or (hd == 128 and G in (1, 2, 4, 8)):
-            if pos_seq is not None:
+            if pos_seq is not None and table is not None:
+                q = llm.qkv_rope_cache_paged(qkv, cos, sin, pos_seq, table, kc, vc, cfg.n_heads)
+                o = llm.decode_attn_paged(q, kc, vc, table, pos_seq)
+            elif pos_seq is not None:
                 q = llm.qkv_rope_cache_seq(qkv, cos, sin, pos_seq, kc, vc, cfg.n_heads)
                 o = llm.decode_attn_seq(q, kc, vc, pos_seq)
             else:
@@ -290,17 +303,19 @@ class Llama(nn.Module):
         return self
 
     def forward_fp8(self, tokens, cache, pos: int = 0, last_only: bool = False, tiled: bool = False,
-                    prefill_attn: bool = False, head: bool = True, seq=None, last_idx=None):
+                    prefill_attn: bool = False, head: bool = True, seq=None, last_idx=None, table=None):
         """``head=False`` (a non-final chunk of a chunked prefill): fill the
         caches only, no final norm / LM head; returns None.  ``seq`` = (pos_t,
         len_t) int32 [B] device tensors: a ragged batch, one position and length
         per sequence.  ``last_idx`` (long [B]): the head runs on token
-        last_idx[b] of sequence b and the result is [B, 1, vocab]."""
+        last_idx[b] of sequence b and the result is [B, 1, vocab].  ``table``
+        (with ``seq``): the block table of a paged cache, see Block.forward_fp8."""
         from ..ops import llm
         cos, sin = self.rope(tokens.device)
         x = self.embed(tokens)
         for i, layer in enumerate(self.layers):
-            x = layer.forward_fp8(x, cos, sin, cache[i], pos, tiled=tiled, prefill_attn=prefill_attn, seq=seq)
+            x = layer.forward_fp8(x, cos, sin, cache[i], pos, tiled=tiled, prefill_attn=prefill_attn, seq=seq,
+                                  table=table)
         if not head:
             return None
         if last_idx is not None:
@@ -310,12 +325,12 @@ class Llama(nn.Module):
         return llm.fp8_linear_q(*llm.rmsnorm_quant_fp8(x, self.norm.weight, self.norm.eps), self._fp8_head,
                                 tiled=tiled)
 
-    def decode_fp8_static(self, tok, cache, pos_i32, pos_i64, mask, pos_seq=None):
+    def decode_fp8_static(self, tok, cache, pos_i32, pos_i64, mask, pos_seq=None, table=None):
         from ..ops import llm
         cos, sin = self.rope(tok.device)
         x = self.embed(tok)
         for i, layer in enumerate(self.layers):
-            x = layer.decode_fp8_static(x, cos, sin, cache[i], pos_i32, pos_i64, mask, pos_seq=pos_seq)
+            x = layer.decode_fp8_static(x, cos, sin, cache[i], pos_i32, pos_i64, mask, pos_seq=pos_seq, table=table)
         return llm.fp8_linear_q(*llm.rmsnorm_quant_fp8(x, self.norm.weight, self.norm.eps), self._fp8_head)
 
     def forward(self, tokens, cache=None, pos: int = 0, fused: bool = False, last_only: bool = False,
@@ -362,7 +377,21 @@ class LlamaDecoder:
 
     def __init__(self, cfg: LlamaConfig, batch: int, context: int, device="cuda", dtype=torch.bfloat16,
                  fused: Optional[bool] = None, fp8: bool = False, graph: bool = False, static: bool = False,
-                 prefill_tiled: bool = False, prefill_attn: bool = False, ragged: bool = False):
+                 prefill_tiled: bool = False, prefill_attn: bool = False, ragged: bool = False,
+                 paged: bool = False, pages: Optional[int] = None, page: int = 64):
+        # opt-in (implies ragged): the KV cache is a pool of `pages` pages of
+        # `page` rows per layer, [pages, Hkv, page, hd], and one block table
+        # [batch, ceil(context / page)] for all layers maps every slot's logical
+        # rows to pages.  A slot holds ceil(pos / page) pages, a request that
+        # does not fit raises PoolExhausted, and admit(..., share=) maps the
+        # full pages of another slot's prefix instead of storing them again.
+        self.paged = paged
+        if paged:
+            ragged = True
+            if page not in (64, 128, 256):
+                raise ValueError(f"LlamaDecoder: page {page!r} must be 64, 128 or 256")
+            if not isinstance(pages, int) or isinstance(pages, bool) or pages < 1:
+                raise ValueError(f"LlamaDecoder: paged=True needs pages, a positive int, got {pages!r}")
         if not 0 < context <= cfg.max_seq:  # the RoPE tables cover max_seq positions
             raise ValueError(f"LlamaDecoder: context {context} must be in [1, max_seq={cfg.max_seq}]")
         # opt-in: every sequence of the batch has a cache position of its own
@@ -412,9 +441,19 @@ class LlamaDecoder:
         self.static = static or graph  # static shapes + device position; graph=True also captures it
         self._g = self._step = None
         hd = cfg.head_dim
-        self.cache = [(torch.zeros(batch, cfg.n_kv_heads, context, hd, device=device, dtype=dtype),
-                       torch.zeros(batch, cfg.n_kv_heads, context, hd, device=device, dtype=dtype))
-                      for _ in range(cfg.n_layers)]
+        if paged:
+            self.page, self.n_table = page, -(-context // page)
+            self.pool = PagePool(pages)
+            self.cache = [(torch.zeros(pages, cfg.n_kv_heads, page, hd, device=device, dtype=dtype),
+                           torch.zeros(pages, cfg.n_kv_heads, page, hd, device=device, dtype=dtype))
+                          for _ in range(cfg.n_layers)]
+            # block table: host mirror (-1 = no page) and the static device tensor the kernels read
+            self._pages = [[] for _ in range(batch)]
+            self._table = torch.full((batch, self.n_table), -1, dtype=torch.int32, device=device)
+        else:
+            self.cache = [(torch.zeros(batch, cfg.n_kv_heads, context, hd, device=device, dtype=dtype),
+                           torch.zeros(batch, cfg.n_kv_heads, context, hd, device=device, dtype=dtype))
+                          for _ in range(cfg.n_layers)]
         self.pos = 0
         # ragged state: cache position of every slot (-1 = idle); self.pos is then
         # the largest active position, for information only
@@ -447,7 +486,11 @@ class LlamaDecoder:
         drained here); needs prefill_attn=True.  ``lens`` (ragged=True): B prompt
         lengths for tokens [B, S] padded to the longest; every slot is reset,
         slot b becomes active with its first lens[b] tokens (0 leaves it idle),
-        in one ragged launch per layer; idle rows of the result are 0."""
+        in one ragged launch per layer; idle rows of the result are 0.
+        paged=True: every form is a ragged prefill (no lens: lens = [S] * B, also
+        with chunk) after ceil(lens[b] / page) pages were found for every slot."""
+        if self.paged:
+            return self._prefill_paged(tokens, chunk, lens)
         if lens is not None:
             if not self.ragged:
                 raise ValueError("LlamaDecoder: lens needs ragged=True")
@@ -495,23 +538,178 @@ class LlamaDecoder:
         tok = logits[:, -1].argmax(-1, keepdim=True)
         return tok * torch.tensor(self.active, device=dev).view(B, 1)
 
+    # ------------------------------------------------------------------ paged cache
+    @property
+    def pages_free(self) -> int:
+        return self.pool.free_pages
+
+    def pages_of(self, slot: int):
+        """Page ids of a slot, in logical order (page i holds rows i page .. (i + 1) page - 1)."""
+        return list(self._pages[slot])
+
+    def _sync_table(self):
+        """Host mirror -> the static device table (as _set_pos for the positions)."""
+        rows = [ids + [-1] * (self.n_table - len(ids)) for ids in self._pages]
+        self._table.copy_(torch.tensor(rows, dtype=torch.int32))
+
+    def _dense_rows(self, slots, rows):
+        """Eager reference: dense caches [len(slots), Hkv, Cl, hd] per layer holding
+        the first rows[i] logical rows of slot slots[i] (zeros elsewhere)."""
+        from ..ops import llm
+        Cl = self.n_table * self.page
+        out = []
+        for kp, vp in self.cache:
+            kc = kp.new_zeros(len(slots), kp.shape[1], Cl, kp.shape[3])
+            vc = torch.zeros_like(kc)
+            for i, (b, n) in enumerate(zip(slots, rows)):
+                if n > 0:
+                    kc[i, :, :n] = llm.paged_gather(kp, self._pages[b], n)
+                    vc[i, :, :n] = llm.paged_gather(vp, self._pages[b], n)
+            out.append((kc, vc))
+        return out
+
+    def _scatter_rows(self, dense, slots, starts, counts):
+        """Eager reference: logical rows starts[i] .. starts[i] + counts[i] - 1 of the
+        dense caches back into the pages of slot slots[i]."""
+        for (kp, vp), (kc, vc) in zip(self.cache, dense):
+            for i, (b, r0, n) in enumerate(zip(slots, starts, counts)):
+                for r in range(r0, r0 + n):
+                    pg, pr = self._pages[b][r // self.page], r % self.page
+                    kp[pg, :, pr] = kc[i, :, r]
+                    vp[pg, :, pr] = vc[i, :, r]
+
+    def _forward_paged(self, tokens, pos, lens, head=True, last_idx=None, slot=None):
+        """One ragged forward over the paged cache: every slot (pos / lens of B
+        ints), or the batch of 1 that is `slot` (one int each).  fp8: the paged
+        kernels on the device table (rows of `slot` alone: a [1, NP] view).
+        Eager: gather, the dense reference path, scatter of the new rows."""
+        slots = list(range(self.batch)) if slot is None else [slot]
+        dev = tokens.device
+        if self.fp8:
+            self._sync_table()
+            seq = (torch.tensor(pos, dtype=torch.int32).to(dev), torch.tensor(lens, dtype=torch.int32).to(dev))
+            table = self._table if slot is None else self._table[slot:slot + 1]
+            return self.model.forward_fp8(tokens, self.cache, 0, last_only=True, tiled=self.prefill_tiled,
+                                          prefill_attn=True, head=head, seq=seq, last_idx=last_idx, table=table)
+        dense = self._dense_rows(slots, [max(p, 0) for p in pos])
+        if slot is None:
+            logits = self.model(tokens, cache=dense, last_only=True, head=head, seq=(list(pos), list(lens)),
+                                last_idx=last_idx)
+        else:  # the uniform reference on the slot alone, as the dense decoder admits a request
+            logits = self.model(tokens, cache=dense, pos=pos[0], fused=False, last_only=True, prefill_attn=True,
+                                head=head)
+        self._scatter_rows(dense, slots, pos, [n if p >= 0 else 0 for p, n in zip(pos, lens)])
+        return logits
+
+    def _prefill_paged(self, tokens: torch.Tensor, chunk, lens) -> torch.Tensor:
+        B, S = tokens.shape
+        if lens is not None and chunk is not None:
+            raise ValueError("LlamaDecoder: lens with chunk is not supported (a ragged prefill is one launch per "
+                             "layer; admit_iter chunks one request)")
+        if lens is None:
+            lens = [S] * B
+        lens = [int(n) for n in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
+        if B != self.batch or len(lens) != B or any(n < 0 or n > S for n in lens):
+            raise ValueError(f"LlamaDecoder: lens {lens} for tokens {tuple(tokens.shape)} and a batch of {self.batch} "
+                             f"(one length in [0, S] per slot)")
+        if max(lens) > self.context:
+            raise ValueError(f"LlamaDecoder: prompt of {max(lens)} tokens for a context of {self.context}")
+        if chunk is not None and (not isinstance(chunk, int) or isinstance(chunk, bool) or chunk < 1):
+            raise ValueError(f"LlamaDecoder: chunk must be a positive int, got {chunk!r}")
+        # every slot is reset: its pages go back first, and come back if the new prompts do not fit
+        snap, held = self.pool.snapshot(), [list(ids) for ids in self._pages]
+        try:
+            for ids in self._pages:
+                self.pool.free(ids)
+            self._pages = [self.pool.alloc(-(-n // self.page)) for n in lens]
+        except PoolExhausted:
+            self.pool.restore(snap)
+            self._pages = held
+            raise
+        dev = tokens.device
+        self.pos_b, self.active = [-1] * B, [False] * B
+        if chunk is None:  # one ragged launch per layer over the padded batch
+            last = torch.tensor([max(n - 1, 0) for n in lens], device=dev)
+            logits = self._forward_paged(tokens, [0 if n else -1 for n in lens], lens, last_idx=last)
+        else:  # lens = [S] * B in pieces: every slot at c0, the head on the last piece
+            for c0 in range(0, S, chunk):
+                c1 = min(S, c0 + chunk)
+                logits = self._forward_paged(tokens[:, c0:c1], [c0] * B, [c1 - c0] * B, head=(c1 == S))
+        self.pos_b = [n if n else -1 for n in lens]
+        self.active = [n > 0 for n in lens]
+        self._sync_pos()
+        tok = logits[:, -1].argmax(-1, keepdim=True)
+        return tok * torch.tensor(self.active, device=dev).view(B, 1)
+
+    def _admit_paged(self, slot: int, tokens: torch.Tensor, chunk: int, share):
+        """Find the pages (shared prefix pages first) at the call; the chunks then
+        run in the generator this returns."""
+        S = tokens.shape[1]
+        shared = []
+        if share is not None:
+            src, n = share
+            if not isinstance(src, int) or isinstance(src, bool) or not 0 <= src < self.batch or src == slot \
+                    or not self.active[src] or not isinstance(n, int) or n < 0:
+                raise ValueError(f"LlamaDecoder: share={share!r} must be (an active slot other than {slot}, tokens)")
+            # full pages only, and at least one token is left to prefill (its logits give the next token)
+            k = min(min(n, self.pos_b[src]) // self.page, (S - 1) // self.page)
+            shared = self._pages[src][:k]
+        snap = self.pool.snapshot()
+        try:
+            self.pool.free(self._pages[slot])  # none, unless an earlier admit_iter of this slot was abandoned
+            fresh = self.pool.alloc(-(-S // self.page) - len(shared))
+        except PoolExhausted:
+            self.pool.restore(snap)  # nothing has changed
+            raise
+        self._pages[slot] = self.pool.share(shared) + fresh
+        return self._admit_chunks_paged(slot, tokens, chunk, len(shared) * self.page)
+
+    def _admit_chunks_paged(self, slot: int, tokens: torch.Tensor, chunk: int, start: int):
+        S = tokens.shape[1]
+        logits = None
+        for c0 in range(start, S, chunk):
+            c1 = min(S, c0 + chunk)
+            with torch.no_grad():
+                logits = self._forward_paged(tokens[:, c0:c1], [c0], [c1 - c0], head=(c1 == S), slot=slot)
+            yield c1
+        self.pos_b[slot], self.active[slot] = S, True
+        self._sync_pos()
+        return logits[:, -1].argmax(-1, keepdim=True)
+
+    def _grow_pages(self):
+        """Before a decode step: a page for every active slot that starts one."""
+        need = [b for b in range(self.batch) if self.active[b] and self.pos_b[b] == len(self._pages[b]) * self.page]
+        if len(need) > self.pool.free_pages:
+            raise PoolExhausted(f"LlamaDecoder: slots {need} start a new page, {self.pool.free_pages} of "
+                                f"{self.pool.pages} pages free; release a slot and retry")
+        for b in need:
+            self._pages[b] += self.pool.alloc(1)
+
     @torch.no_grad()
-    def admit(self, slot: int, tokens: torch.Tensor, chunk: Optional[int] = None) -> torch.Tensor:
+    def admit(self, slot: int, tokens: torch.Tensor, chunk: Optional[int] = None, share=None) -> torch.Tensor:
         """Prefill one request (tokens [S] or [1, S]) into the idle slot `slot`
         while the other slots keep their state; returns its next token [1, 1].
-        ``chunk``: as admit_iter, drained here."""
+        ``chunk`` / ``share``: as admit_iter, drained here."""
         n = tokens.shape[-1]
-        return self._drain(self.admit_iter(slot, tokens, n if chunk is None else chunk))
+        return self._drain(self.admit_iter(slot, tokens, n if chunk is None else chunk, share=share))
 
-    def admit_iter(self, slot: int, tokens: torch.Tensor, chunk: int):
+    def admit_iter(self, slot: int, tokens: torch.Tensor, chunk: int, share=None):
         """admit() as a generator over chunks of at most `chunk` tokens (the
         uniform chunked prefill on the batch-1 views of the slot's caches): yields
         the prompt tokens done after each chunk, so a scheduled tenant gives every
         chunk a slice of its own and decode steps of the other slots may run in
         between; the slot stays idle until the last chunk is done.  The next
-        token [1, 1] is the generator's return value."""
+        token [1, 1] is the generator's return value.
+        paged=True: the prompt's pages are found here, at the call (PoolExhausted
+        if they are not there), and the chunks run the paged kernels on the
+        slot's own table row.  ``share`` = (src, n) maps the first
+        floor(min(n, pos_b[src]) / page) pages of the active slot src into this
+        slot instead of storing them again (the caller asserts the two prompts
+        agree on those tokens) and prefill starts after them."""
         if not self.ragged:
             raise ValueError("LlamaDecoder: admit needs ragged=True")
+        if share is not None and not self.paged:
+            raise ValueError("LlamaDecoder: share needs paged=True")
         if not isinstance(slot, int) or isinstance(slot, bool) or not 0 <= slot < self.batch:
             raise ValueError(f"LlamaDecoder: slot {slot!r} of a batch of {self.batch}")
         if self.active[slot]:
@@ -522,6 +720,8 @@ class LlamaDecoder:
         S = tokens.shape[1]
         if not 0 < S <= self.context:
             raise ValueError(f"LlamaDecoder: prompt of {S} tokens for a context of {self.context}")
+        if self.paged:
+            return self._admit_paged(slot, tokens, chunk, share)
         return self._admit_chunks(slot, tokens, chunk)
 
     def _admit_chunks(self, slot: int, tokens: torch.Tensor, chunk: int):
@@ -533,9 +733,13 @@ class LlamaDecoder:
         return tok
 
     def release(self, slot: int):
-        """Mark a slot idle (its request is done); the cache rows stay as they are."""
+        """Mark a slot idle (its request is done); the cache rows stay as they are.
+        paged=True: its pages lose this slot's reference (contents not cleared)."""
         if not self.ragged:
             raise ValueError("LlamaDecoder: release needs ragged=True")
+        if self.paged:
+            self.pool.free(self._pages[slot])
+            self._pages[slot] = []
         self.pos_b[slot], self.active[slot] = -1, False
         self._sync_pos()
 
@@ -580,7 +784,8 @@ class LlamaDecoder:
             self._pos_seq = torch.full((self.batch,), -1, dtype=torch.int32, device=dev)
 
             def step():
-                logits = self.model.decode_fp8_static(self._tok, self.cache, None, None, None, pos_seq=self._pos_seq)
+                logits = self.model.decode_fp8_static(self._tok, self.cache, None, None, None, pos_seq=self._pos_seq,
+                                                      table=self._table if self.paged else None)
                 return logits[:, -1].argmax(-1, keepdim=True)
         else:
             self._pos_i32 = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -609,6 +814,8 @@ class LlamaDecoder:
     def _set_pos(self):
         if self.ragged:
             self._pos_seq.copy_(torch.tensor(self.pos_b, dtype=torch.int32))
+            if self.paged:  # the captured graph reads the same table tensor: admission, release, growth survive
+                self._sync_table()
             return
         self._pos_i32.fill_(self.pos)
         self._pos_i64.fill_(self.pos)
@@ -618,6 +825,8 @@ class LlamaDecoder:
             if self.active[b] and self.pos_b[b] >= self.context:
                 raise ValueError(f"LlamaDecoder: slot {b} is at position {self.pos_b[b]} = context; release it (ragged "
                                  f"mode has no sliding window)")
+        if self.paged:
+            self._grow_pages()  # before any launch; PoolExhausted leaves everything as it was
         if self.fp8:
             if self._step is None:
                 self._graph_setup(tok)
@@ -628,6 +837,9 @@ class LlamaDecoder:
                 out = self._out.clone()
             else:
                 out = self._step()
+        elif self.paged:
+            logits = self._forward_paged(tok, list(self.pos_b), [int(a) for a in self.active])
+            out = logits[:, -1].argmax(-1, keepdim=True)
         else:
             logits = self._forward(tok, 0, seq=(list(self.pos_b), [int(a) for a in self.active]))
             out = logits[:, -1].argmax(-1, keepdim=True)

@@ -420,6 +420,187 @@ def attn_seq_ref(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, pos, lens)
     return out
 
 
+# --------------------------------------------------------------------------- paged KV cache (block-table kernels)
+# The _seq kernels over pools kpool / vpool bf16 [P, Hkv, page, 128] and an int32
+# block table [B, NP] on the device: logical row r of sequence b lives in page
+# table[b, r // page] at page row r % page.  Cl = NP * page takes the place of C
+# in the slot rules above.  The kernels read only the table entries of pages
+# that hold rows 0 .. pos[b] (decode) or 0 .. pos[b] + n_b - 1 (prefill): the
+# tail of a table row, and the whole row of an idle slot, may hold anything.  A
+# read entry outside [0, P) forms no address outside the pools: the write
+# through it is dropped, the reads through it come from page 0.
+PAGE_SIZES = (64, 128, 256)
+
+
+def _need_paged(what: str, kpool: torch.Tensor, vpool: torch.Tensor, table: torch.Tensor, B: Optional[int] = None):
+    """Host-side checks of the pools and the block table; returns
+    (B, NP, P, Hkv, page, hd).  The table's values are not read (as _need_seq)."""
+    if not isinstance(kpool, torch.Tensor) or not isinstance(vpool, torch.Tensor) or kpool.dim() != 4 \
+            or vpool.shape != kpool.shape:
+        raise ValueError(f"{what}: pools {tuple(getattr(kpool, 'shape', ()))} / {tuple(getattr(vpool, 'shape', ()))} "
+                         f"must be [P, Hkv, page, 128] of one shape")
+    P, Hkv, page, hd = kpool.shape
+    if page not in PAGE_SIZES or hd != 128 or P < 1 or Hkv < 1:
+        raise ValueError(f"{what}: pools {tuple(kpool.shape)} must be [P, Hkv, page, 128] with page in {PAGE_SIZES}")
+    for name, t in (("kpool", kpool), ("vpool", vpool)):
+        if t.dtype != torch.bfloat16 or not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be contiguous bf16, got {t.dtype} strides {t.stride()}")
+    if not isinstance(table, torch.Tensor) or table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] < 1 \
+            or (B is not None and table.shape[0] != B):
+        raise ValueError(f"{what}: table must be an int32 tensor [B{'' if B is None else '=' + str(B)}, NP >= 1], got "
+                         f"{getattr(table, 'dtype', type(table))} {tuple(getattr(table, 'shape', ()))}")
+    if not table.is_contiguous():
+        raise ValueError(f"{what}: table must be contiguous (strides {table.stride()})")
+    if not table.is_cuda:
+        raise ValueError(f"{what}: table must be a CUDA tensor (the kernel reads it), got {table.device}")
+    _need(kpool, f"{what} kpool")
+    _need(vpool, f"{what} vpool")
+    return table.shape[0], table.shape[1], P, Hkv, page, hd
+
+
+def qkv_rope_cache_paged(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos_t: torch.Tensor,
+                         table: torch.Tensor, kpool: torch.Tensor, vpool: torch.Tensor, n_heads: int) -> torch.Tensor:
+    """qkv_rope_cache_seq through a block table: an active sequence
+    (0 <= pos_t[b] < NP * page) gets the same q and writes the same k / v row,
+    into row pos_t[b] % page of page table[b, pos_t[b] // page]."""
+    what = "qkv_rope_cache_paged"
+    B, NP, P, Hkv, page, hd = _need_paged(what, kpool, vpool, table)
+    Cl = NP * page
+    _need_seq(what, B, pos_t=pos_t)
+    _need(qkv, f"{what} qkv")
+    if qkv.numel() != B * (n_heads + 2 * Hkv) * hd or cos.dim() != 2 or cos.shape[-1] * 2 != hd:
+        raise ValueError(f"{what}: qkv {tuple(qkv.shape)} vs pools {tuple(kpool.shape)}, B={B}, H={n_heads}")
+    if cos.shape[0] < Cl or sin.shape != cos.shape or cos.dtype != torch.float32 or sin.dtype != torch.float32 \
+            or not (cos.is_cuda and sin.is_cuda and cos.is_contiguous() and sin.is_contiguous()):
+        raise ValueError(f"{what}: rope tables {tuple(cos.shape)} {cos.dtype} must be contiguous fp32 CUDA tensors "
+                         f"covering NP * page = {Cl} rows")
+    q = torch.empty(B, n_heads, hd, dtype=torch.bfloat16, device=qkv.device)
+    _check(lib().gpbs_hip_qkv_rope_cache_paged(_ptr(qkv), _ptr(cos), _ptr(sin), _ptr(pos_t), _ptr(table), _ptr(q),
+                                               _ptr(kpool), _ptr(vpool), B, n_heads, Hkv, NP, P, page, hd, _stream()),
+           what)
+    return q
+
+
+def decode_attn_paged(q: torch.Tensor, kpool: torch.Tensor, vpool: torch.Tensor, table: torch.Tensor,
+                      pos_t: torch.Tensor, nsplit: Optional[int] = None) -> torch.Tensor:
+    """decode_attn_seq through a block table: row b is bit-identical to
+    decode_attn_seq on the dense cache of Cl = NP * page rows gathered from
+    sequence b's pages, with the same nsplit (default: from (B, Hkv, Cl))."""
+    what = "decode_attn_paged"
+    B, NP, P, Hkv, page, hd = _need_paged(what, kpool, vpool, table)
+    Cl = NP * page
+    if q.dim() != 3 or q.shape[0] != B or q.shape[2] != hd:
+        raise ValueError(f"{what}: q {tuple(q.shape)} must be [B={B}, H, 128]")
+    H = q.shape[1]
+    if H % Hkv or (H // Hkv) not in (1, 2, 4, 8):
+        raise ValueError(f"{what}: group size H / Hkv = {H} / {Hkv} must be 1, 2, 4 or 8")
+    if q.dtype != torch.bfloat16 or not q.is_contiguous():
+        raise ValueError(f"{what}: q must be contiguous bf16, got {q.dtype} strides {q.stride()}")
+    if nsplit is not None and (not isinstance(nsplit, int) or isinstance(nsplit, bool) or nsplit < 1):
+        raise ValueError(f"{what}: nsplit={nsplit!r} must be None or an int >= 1")
+    _need_seq(what, B, pos_t=pos_t)
+    _need(q, f"{what} q")
+    out = torch.empty(B, H * hd, dtype=torch.bfloat16, device=q.device)
+    if nsplit is None:  # as decode_attn_seq, with Cl for C
+        nsplit = max(1, min(8, -(-256 // (B * Hkv)), -(-Cl // 64)))
+    ws = torch.empty(B * Hkv * nsplit * (H // Hkv) * (hd + 2), dtype=torch.float32, device=q.device) \
+        if nsplit > 1 else None
+    _check(lib().gpbs_hip_decode_attn_paged(_ptr(q), _ptr(kpool), _ptr(vpool), _ptr(pos_t), _ptr(table), _ptr(out),
+                                            _ptr(ws), nsplit, B, H, Hkv, NP, P, page, hd, C.c_float(hd ** -0.5),
+                                            _stream()), what)
+    return out
+
+
+def qkv_rope_cache_prefill_paged(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos_t: torch.Tensor,
+                                 len_t: torch.Tensor, table: torch.Tensor, kpool: torch.Tensor, vpool: torch.Tensor,
+                                 n_heads: int) -> torch.Tensor:
+    """qkv_rope_cache_prefill_seq through a block table: token s < n_b of
+    sequence b (n_b from Cl = NP * page) is written to logical row pos_t[b] + s
+    of its pages.  Returns q [B, S, H, hd]."""
+    what = "qkv_rope_cache_prefill_paged"
+    B, NP, P, Hkv, page, hd = _need_paged(what, kpool, vpool, table)
+    Cl = NP * page
+    if qkv.dim() != 3 or qkv.shape[0] != B or qkv.shape[1] < 1 or qkv.shape[2] != (n_heads + 2 * Hkv) * hd \
+            or cos.dim() != 2 or cos.shape[-1] * 2 != hd:
+        raise ValueError(f"{what}: qkv {tuple(qkv.shape)} must be [B={B}, S, (H + 2 Hkv) hd] for pools "
+                         f"{tuple(kpool.shape)}, H={n_heads}, rope tables {tuple(cos.shape)}")
+    S = qkv.shape[1]
+    _need_seq(what, B, pos_t=pos_t, len_t=len_t)
+    if cos.shape[0] < Cl or sin.shape != cos.shape or cos.dtype != torch.float32 or sin.dtype != torch.float32 \
+            or not (cos.is_contiguous() and sin.is_contiguous()):
+        raise ValueError(f"{what}: rope tables {tuple(cos.shape)} {cos.dtype} must be contiguous fp32 and cover "
+                         f"NP * page = {Cl} rows")
+    if qkv.dtype != torch.bfloat16 or not qkv.is_contiguous():
+        raise ValueError(f"{what}: qkv must be contiguous bf16, got {qkv.dtype} strides {qkv.stride()}")
+    _need(qkv, f"{what} qkv")
+    if not (cos.is_cuda and sin.is_cuda):
+        raise ValueError(f"{what}: rope tables must be CUDA tensors")
+    q = torch.empty(B, S, n_heads, hd, dtype=torch.bfloat16, device=qkv.device)
+    _check(lib().gpbs_hip_qkv_rope_cache_prefill_paged(_ptr(qkv), _ptr(cos), _ptr(sin), _ptr(pos_t), _ptr(len_t),
+                                                       _ptr(table), _ptr(q), _ptr(kpool), _ptr(vpool), B, S, n_heads,
+                                                       Hkv, NP, P, page, hd, _stream()), what)
+    return q
+
+
+def prefill_attn_paged(q: torch.Tensor, kpool: torch.Tensor, vpool: torch.Tensor, table: torch.Tensor,
+                       pos_t: torch.Tensor, len_t: torch.Tensor) -> torch.Tensor:
+    """prefill_attn_seq through a block table: rows s < n_b of sequence b are
+    bit-identical to prefill_attn_seq on the dense cache gathered from its
+    pages; no row past pos_t[b] + n_b - 1 is addressed, through any page.
+    Returns [B, S, H * 128] bf16, rows s >= n_b zero."""
+    what = "prefill_attn_paged"
+    B, NP, P, Hkv, page, hd = _need_paged(what, kpool, vpool, table)
+    if q.dim() != 4 or q.shape[0] != B or q.shape[1] < 1 or q.shape[3] != hd:
+        raise ValueError(f"{what}: q {tuple(q.shape)} must be [B={B}, S, H, 128]")
+    S, H = q.shape[1], q.shape[2]
+    if H % Hkv or (H // Hkv) not in (1, 2, 4, 8):
+        raise ValueError(f"{what}: group size H / Hkv = {H} / {Hkv} must be 1, 2, 4 or 8")
+    if q.dtype != torch.bfloat16 or not q.is_contiguous():
+        raise ValueError(f"{what}: q must be contiguous bf16, got {q.dtype} strides {q.stride()}")
+    _need_seq(what, B, pos_t=pos_t, len_t=len_t)
+    _need(q, f"{what} q")
+    out = torch.zeros(B, S, H * hd, dtype=torch.bfloat16, device=q.device)  # the kernel stores rows < n_b only
+    _check(lib().gpbs_hip_prefill_attn_paged(_ptr(q), _ptr(kpool), _ptr(vpool), _ptr(pos_t), _ptr(len_t), _ptr(table),
+                                             _ptr(out), B, S, H, Hkv, NP, P, page, hd, C.c_float(hd ** -0.5),
+                                             _stream()), what)
+    return out
+
+
+def paged_gather(pool: torch.Tensor, table_row, rows: int) -> torch.Tensor:
+    """Logical rows 0 .. rows - 1 of one sequence as a dense [Hkv, rows, hd]
+    tensor: row r is pool[table_row[r // page], :, r % page].  Plain torch, any
+    device; only the first ceil(rows / page) entries of table_row are read."""
+    P, Hkv, page, hd = pool.shape
+    n = -(-rows // page)
+    ids = [int(e) for e in (table_row.tolist() if isinstance(table_row, torch.Tensor) else table_row)][:n]
+    if len(ids) < n or any(not 0 <= e < P for e in ids):
+        raise ValueError(f"paged_gather: {rows} rows need {n} table entries in [0, {P}), got {ids}")
+    if not n:
+        return pool.new_zeros(Hkv, 0, hd)
+    idx = torch.tensor(ids, dtype=torch.long, device=pool.device)
+    return pool[idx].permute(1, 0, 2, 3).reshape(Hkv, n * page, hd)[:, :rows]
+
+
+def attn_paged_ref(q: torch.Tensor, kpool: torch.Tensor, vpool: torch.Tensor, table, pos, lens) -> torch.Tensor:
+    """Plain-torch reference of prefill_attn_paged (and, with S = 1 and lens = 1
+    for the active slots, of decode_attn_paged): each active sequence's rows
+    gathered into dense caches of Cl = NP * page rows, then attn_seq_ref."""
+    B, S, H, hd = q.shape
+    P, Hkv, page, _ = kpool.shape
+    table = torch.as_tensor(table)
+    NP = table.shape[1]
+    Cl = NP * page
+    pos = [int(p) for p in (pos.tolist() if isinstance(pos, torch.Tensor) else pos)]
+    lens = [int(n) for n in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
+    kc, vc = kpool.new_zeros(B, Hkv, Cl, hd), vpool.new_zeros(B, Hkv, Cl, hd)
+    for b in range(B):
+        n = seq_tokens(pos[b], lens[b], S, Cl)
+        if n:
+            kc[b, :, :pos[b] + n] = paged_gather(kpool, table[b], pos[b] + n)
+            vc[b, :, :pos[b] + n] = paged_gather(vpool, table[b], pos[b] + n)
+    return attn_seq_ref(q, kc, vc, pos, lens)
+
+
 # --------------------------------------------------------------------------- fp8 (config #5, CDNA4 fp8 MFMA)
 FP8_MAX = 448.0  # OCP e4m3fn (gfx950), not the MI300 fnuz variant
 FP8_M_TILE = 64  # rows per gpbs_hip_fp8_linear launch

@@ -17,6 +17,17 @@ uniform kernel against itself; decode_attn_seq with lengths spread over
 prefill_attn at S 1024.
 
     python scripts/attn_bench.py --ragged [--iters 100] [--out profiles/ragged_attn.jsonl]
+
+--paged runs instead the block-table kernels against their per-sequence twins at
+the same shapes (B 8, 8192 rows per sequence): the dense cache is scattered into
+pools of 64-, 128- and 256-row pages, once under the identity table (page i of
+sequence b is pool page b NP + i, the dense layout) and once under a shuffled
+one; decode_attn_paged against decode_attn_seq with every length 8192 and with
+lengths 1024..8192, prefill_attn_paged against prefill_attn_seq at S 1024.  The
+_seq twin is timed in the same rounds, twice, so the rows carry its spread
+against itself.
+
+    python scripts/attn_bench.py --paged [--iters 100] [--out profiles/paged_attn.jsonl]
 """
 import argparse
 import json
@@ -201,6 +212,65 @@ def ragged_rows(emit, g, iters, B=8, C=8192):
         emit(rec)
 
 
+def paged_rows(emit, g, iters, B=8, C=8192, pages=(64, 128, 256)):
+    i32 = dict(dtype=torch.int32, device="cuda")
+    q = torch.randn(B, H, HD, device="cuda", generator=g).bfloat16()
+    kc = torch.randn(B, HKV, C, HD, device="cuda", generator=g).bfloat16()
+    vc = torch.randn(B, HKV, C, HD, device="cuda", generator=g).bfloat16()
+    full = torch.full((B,), C - 1, **i32)
+    spread_l = [1024 + (C - 1024) * b // (B - 1) for b in range(B)]
+    spread = torch.tensor([n - 1 for n in spread_l], **i32)
+    S = 1024
+    qp = torch.randn(B, S, H, HD, device="cuda", generator=g).bfloat16()
+    zeros, all_s = torch.zeros(B, **i32), torch.full((B,), S, **i32)
+    variants = {
+        "decode_attn_seq all 8192 (first)": lambda: llm.decode_attn_seq(q, kc, vc, full),
+        "decode_attn_seq 1024..8192": lambda: llm.decode_attn_seq(q, kc, vc, spread),
+        "prefill_attn_seq all 1024 (first)": lambda: llm.prefill_attn_seq(qp, kc, vc, zeros, all_s),
+    }
+    base, info = {}, {}
+    for page in pages:
+        NP = C // page
+        for kind in ("identity", "shuffled"):
+            ids = torch.arange(B * NP, device="cuda")
+            if kind == "shuffled":
+                ids = ids[torch.randperm(B * NP, device="cuda", generator=g)]
+            table = ids.view(B, NP).to(torch.int32).contiguous()
+            # pool page table[b, i] holds rows i page .. (i + 1) page - 1 of sequence b
+            kp, vp = (torch.empty(B * NP, HKV, page, HD, device="cuda", dtype=torch.bfloat16) for _ in range(2))
+            for pool, dense in ((kp, kc), (vp, vc)):
+                pool[ids] = dense.view(B, HKV, NP, page, HD).permute(0, 2, 1, 3, 4).reshape(B * NP, HKV, page, HD)
+            tag = f"page {page} {kind}"
+            for name, over, fn in (
+                    (f"decode_attn_paged all 8192, {tag}", "decode_attn_seq all 8192 (first)",
+                     lambda kp=kp, vp=vp, table=table: llm.decode_attn_paged(q, kp, vp, table, full)),
+                    (f"decode_attn_paged 1024..8192, {tag}", "decode_attn_seq 1024..8192",
+                     lambda kp=kp, vp=vp, table=table: llm.decode_attn_paged(q, kp, vp, table, spread)),
+                    (f"prefill_attn_paged all 1024, {tag}", "prefill_attn_seq all 1024 (first)",
+                     lambda kp=kp, vp=vp, table=table: llm.prefill_attn_paged(qp, kp, vp, table, zeros, all_s))):
+                variants[name], base[name] = fn, over
+                info[name] = {"page": page, "table": kind}
+                assert torch.equal(fn(), variants[over]()), name  # bit for bit before anything is timed
+    variants["decode_attn_seq all 8192 (second)"] = variants["decode_attn_seq all 8192 (first)"]
+    variants["prefill_attn_seq all 1024 (second)"] = variants["prefill_attn_seq all 1024 (first)"]
+    base["decode_attn_seq all 8192 (second)"] = "decode_attn_seq all 8192 (first)"
+    base["prefill_attn_seq all 1024 (second)"] = "prefill_attn_seq all 1024 (first)"
+    times = {k: [] for k in variants}
+    for _ in range(ROUNDS):  # the variants alternate within a round
+        for k, fn in variants.items():
+            times[k].append(timeit(fn, iters))
+    m = {k: med(v) for k, v in times.items()}
+    for k in variants:
+        rec = {"bench": "paged_attn", "name": k, "B": B, "rows": C, "H": H, "Hkv": HKV, "us": round(m[k], 1),
+               "us_minmax": [round(min(times[k]), 1), round(max(times[k]), 1)]}
+        if k in base:
+            r = [t / u for t, u in zip(times[k], times[base[k]])]  # per round: both timed within the same round
+            rec.update({"over": base[k], "ratio": round(med(r), 3),
+                        "ratio_minmax": [round(min(r), 3), round(max(r), 3)]})
+        rec.update(info.get(k, {}))
+        emit(rec)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=100)
@@ -208,6 +278,7 @@ def main():
     ap.add_argument("--skip-model", action="store_true")
     ap.add_argument("--skip-kernel", action="store_true")
     ap.add_argument("--ragged", action="store_true", help="only the per-sequence kernels against their uniform twins")
+    ap.add_argument("--paged", action="store_true", help="only the block-table kernels against their _seq twins")
     a = ap.parse_args()
     out = open(a.out, "a") if a.out else None
 
@@ -220,6 +291,9 @@ def main():
     g = torch.Generator(device="cuda").manual_seed(0)
     if a.ragged:
         ragged_rows(emit, g, a.iters)
+        return
+    if a.paged:
+        paged_rows(emit, g, a.iters)
         return
     if not a.skip_kernel:
         kernel_row(emit, g, a.iters, 8, 1024, 0, 2048, "llm5 prompt")
