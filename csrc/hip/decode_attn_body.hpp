@@ -1,5 +1,5 @@
 // The decode attention kernel and its combine kernel.  Not a header of its own:
-// decode_kernels.hip includes this text three times, inside namespace gpbs_dec, with
+// decode_kernels.hip includes this text four times, inside namespace gpbs_dec, with
 // GPBS_SEQ 0 (k_decode_attn, k_decode_attn_combine: one device position for
 // the batch) and GPBS_SEQ 1 (k_decode_attn_seq, k_decode_attn_combine_seq: dpos
 // is int32 [B]; sequence b has L = dpos[b] + 1 keys if 0 <= dpos[b] < C and is
@@ -12,7 +12,15 @@
 // so the only new work is one wave-uniform table entry per step, loaded one
 // step ahead; an entry outside [0, P) reads page 0.  It emits no combine
 // kernel: k_decode_attn_combine_seq touches no cache and serves it as it is.
-#if GPBS_SEQ == 2
+// GPBS_SEQ 3 is a fourth compilation, k_decode_attn_paged_kv8: the paged kernel
+// over e4m3 pools (one byte per element) with one power-of-two fp32 scale per
+// (page, KV head, page row).  A lane's key row is 8 16-byte loads and its scale,
+// the V piece of a (key, dl) 8 bytes and that key's scale; code times scale is
+// exact and is a bf16 value, so kv8_words rebuilds the very words the dequantised
+// bf16 pools hold, and everything from bfl / bfh on is shared text.
+#if GPBS_SEQ == 3
+#define GPBS_DEC_ATTN k_decode_attn_paged_kv8
+#elif GPBS_SEQ == 2
 #define GPBS_DEC_ATTN k_decode_attn_paged
 #elif GPBS_SEQ
 #define GPBS_DEC_ATTN k_decode_attn_seq
@@ -26,8 +34,14 @@
 template <int G>
 __global__ __launch_bounds__(kAttnWaves * 64) void GPBS_DEC_ATTN(const u32x4* __restrict__ q,
                                                                const u32x4* __restrict__ kc,
+#if GPBS_SEQ == 3
+                                                               const u32x2* __restrict__ vc,
+                                                               const float* __restrict__ ksc,
+                                                               const float* __restrict__ vsc,
+#else
                                                                const u32* __restrict__ vc,
-#if GPBS_SEQ == 2
+#endif
+#if GPBS_SEQ >= 2
                                                                const int* __restrict__ dpos,
                                                                const int* __restrict__ table, u32* __restrict__ out,
                                                                float* __restrict__ ws, int Hkv, int NP, int P, int psh,
@@ -65,10 +79,18 @@ __global__ __launch_bounds__(kAttnWaves * 64) void GPBS_DEC_ATTN(const u32x4* __
     }
   }
   __syncthreads();
-#if GPBS_SEQ == 2
+#if GPBS_SEQ >= 2
+#if GPBS_SEQ == 3
+  // the bases of KV head kvh in page 0: 128-byte rows of codes, one scale per row
+  const u32x4* kh = kc + ((size_t)kvh << psh) * (kHd / 16);
+  const u32x2* vh = vc + ((size_t)kvh << psh) * (kHd / 8);
+  const float* ksh = ksc + ((size_t)kvh << psh);
+  const float* vsh = vsc + ((size_t)kvh << psh);
+#else
   // the bases of KV head kvh in page 0; a page is Hkv << psh rows further on
   const u32x4* kh = kc + ((size_t)kvh << psh) * (kHd / 8);
   const u32* vh = vc + ((size_t)kvh << psh) * (kHd / 2);
+#endif
   const int* trow = table + (size_t)b * NP;
   const int base0 = __builtin_amdgcn_readfirstlane(k0 + w * 64);
   int pg = base0 < k1 ? page_or0(trow[base0 >> psh], P) : 0;  // the page of this wave's first step
@@ -88,7 +110,7 @@ __global__ __launch_bounds__(kAttnWaves * 64) void GPBS_DEC_ATTN(const u32x4* __
     for (int e = 0; e < 8; ++e) o[g][e] = 0.f;
   }
 
-#if GPBS_SEQ == 2
+#if GPBS_SEQ >= 2
   for (int base = base0; base < k1; base += kAttnWaves * 64) {
     // rows of this step within the pools: page pg, page rows base % page ..; the
     // next step's entry (only if that step has keys) is in flight under this one
@@ -107,6 +129,13 @@ __global__ __launch_bounds__(kAttnWaves * 64) void GPBS_DEC_ATTN(const u32x4* __
     asm volatile("" : "+s"(z));
     const float* qz = &qs[0][0] + z;
     if (j < k1) {
+#if GPBS_SEQ == 3
+      const u32x4* kr = kh + (prow + lane) * (kHd / 16);
+      u32x4 krow[kHd / 16];  // the lane's whole 128-byte key row in flight at once, and its scale
+#pragma unroll
+      for (int c = 0; c < kHd / 16; ++c) krow[c] = kr[c];
+      const float ks = ksh[prow + lane];
+#else
 #if GPBS_SEQ == 2
       const u32x4* kr = kh + (prow + lane) * (kHd / 8);
 #else
@@ -115,9 +144,15 @@ __global__ __launch_bounds__(kAttnWaves * 64) void GPBS_DEC_ATTN(const u32x4* __
       u32x4 krow[kHd / 8];  // the lane's whole 256-byte key row in flight at once
 #pragma unroll
       for (int c = 0; c < kHd / 8; ++c) krow[c] = kr[c];
+#endif
 #pragma unroll
       for (int c = 0; c < kHd / 8; ++c) {
+#if GPBS_SEQ == 3
+        // dims 8 c .. 8 c + 7 are words 2 (c & 1), + 1 of the row's 16-byte piece c >> 1
+        const u32x4 kv = kv8_words(u32x2{krow[c >> 1][2 * (c & 1)], krow[c >> 1][2 * (c & 1) + 1]}, ks);
+#else
         const u32x4 kv = krow[c];
+#endif
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           const float k0 = bfl(kv[k]), k1 = bfh(kv[k]);
@@ -140,7 +175,10 @@ __global__ __launch_bounds__(kAttnWaves * 64) void GPBS_DEC_ATTN(const u32x4* __
       m[g] = mn;
     }
     // PV: 16 rounds of 4 keys (one per key group), 16-byte V loads, weights by shuffle
-#if GPBS_SEQ == 2
+#if GPBS_SEQ == 3
+    const u32x2* vb = vh + prow * (kHd / 8) + dl;
+    const float* vsb = vsh + prow;
+#elif GPBS_SEQ == 2
     const u32x4* vb = reinterpret_cast<const u32x4*>(vh) + prow * (kHd / 8) + dl;
 #else
     const u32x4* vb = reinterpret_cast<const u32x4*>(vh) + (size_t)base * (kHd / 8) + dl;
@@ -152,7 +190,11 @@ __global__ __launch_bounds__(kAttnWaves * 64) void GPBS_DEC_ATTN(const u32x4* __
 #pragma unroll
       for (int g = 0; g < G; ++g) pj[g] = __shfl(p[g], jj, 64);
       if (jj < nk) {
+#if GPBS_SEQ == 3
+        const u32x4 vv = kv8_words(vb[(size_t)jj * (kHd / 8)], vsb[jj]);  // 8 codes: dims 8 dl .. 8 dl + 7
+#else
         const u32x4 vv = vb[(size_t)jj * (kHd / 8)];
+#endif
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const float v0 = bfl(vv[e]), v1 = bfh(vv[e]);
@@ -210,7 +252,7 @@ __global__ __launch_bounds__(kAttnWaves * 64) void GPBS_DEC_ATTN(const u32x4* __
   }
 }
 
-#if GPBS_SEQ != 2
+#if GPBS_SEQ < 2
 // Merge the nsplit partials of each (batch, KV head): grid B * Hkv, G * 64 threads.
 __global__ __launch_bounds__(512) void GPBS_DEC_COMBINE(const float* __restrict__ ws, u32* __restrict__ out,
                                                              int Hkv, int G, int nsplit) {

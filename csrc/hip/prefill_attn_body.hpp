@@ -1,5 +1,5 @@
 // The prefill attention kernel.  Not a header of its own: prefill_kernels.hip
-// includes this text three times, inside namespace gpbs_pf, with GPBS_SEQ 0
+// includes this text four times, inside namespace gpbs_pf, with GPBS_SEQ 0
 // (k_prefill_attn: S and pos are kernel arguments) and GPBS_SEQ 1
 // (k_prefill_attn_seq: the launch is sized for Sq tokens per sequence, the row
 // stride of q / out, and a workgroup takes pos = posb[b] and S = n_b, the tokens
@@ -15,6 +15,13 @@
 // krow_last, so the only new work is one workgroup-uniform table entry per
 // tile, loaded one prefetch ahead of the rows it addresses; an entry outside
 // [0, P) reads page 0.
+// GPBS_SEQ 3 is a fourth compilation, k_prefill_attn_paged_kv8: the paged kernel
+// over e4m3 pools (one byte per element) with one power-of-two fp32 scale per
+// (page, KV head, page row).  The prefetch registers hold 8-byte pieces and their
+// rows' scales; a piece becomes its 16 bytes of bf16 (kv8_dequant8: exact) where
+// it is stored to LDS, so the loads stay in flight under the MFMAs and the K and
+// V images, and with them everything from the first LDS read on, are those of
+// the paged kernel on the dequantised pools.
 #if GPBS_SEQ
 #define GPBS_PF_STRIDE Sq
 #else
@@ -23,7 +30,20 @@
 
 // q [B, S, H, 128], caches [B, Hkv, C, 128], out [B, S, H * 128]; H = G * Hkv.
 template <int G>
-#if GPBS_SEQ == 2
+#if GPBS_SEQ == 3
+__global__ __launch_bounds__(kWaves * 64) void k_prefill_attn_paged_kv8(const u32x4* __restrict__ q,
+                                                                        const u32x2* __restrict__ kc,
+                                                                        const u32x2* __restrict__ vc,
+                                                                        const float* __restrict__ ksc,
+                                                                        const float* __restrict__ vsc,
+                                                                        const int* __restrict__ posb,
+                                                                        const int* __restrict__ lenb,
+                                                                        const int* __restrict__ table,
+                                                                        u32x2* __restrict__ out, int Sq, int Hkv,
+                                                                        int NP, int P, int psh, float scale_log2e,
+                                                                        int nbh) {
+  const int C = NP << psh;  // the logical context Cl
+#elif GPBS_SEQ == 2
 __global__ __launch_bounds__(kWaves * 64) void k_prefill_attn_paged(const u32x4* __restrict__ q,
                                                                     const u32x4* __restrict__ kc,
                                                                     const u32x4* __restrict__ vc,
@@ -80,7 +100,7 @@ __global__ __launch_bounds__(kWaves * 64) void k_prefill_attn(const u32x4* __res
 
   // staging: piece i of this thread is chunk sch of tile row srow + 32 i
   const int srow = tid >> 4, sch = tid & 15;
-#if GPBS_SEQ == 2
+#if GPBS_SEQ >= 2
   // row r of tile t sits in page table[b, t kKT / page] at page row r % page;
   // pgn is the entry of the tile the next prefetch loads, fetched one tile ahead
   const int* trow = table + (size_t)b * NP;
@@ -92,16 +112,25 @@ __global__ __launch_bounds__(kWaves * 64) void k_prefill_attn(const u32x4* __res
 #else
   const size_t head = ((size_t)b * Hkv + kvh) * C;
 #endif
+#if GPBS_SEQ == 3
+  u32x2 kr[2], vr[2];  // 8 codes each, and the scales of their rows
+  float ksr[2], vsr[2];
+#else
   u32x4 kr[2], vr[2];
+#endif
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
-#if GPBS_SEQ == 2
+#if GPBS_SEQ >= 2
     const size_t row = head + pg0 * pstride + min(srow + 32 * i, krow_last);  // tile 0: page row == row
 #else
     const size_t row = head + min(srow + 32 * i, krow_last);
 #endif
     kr[i] = kc[row * (kHd / 8) + sch];
     vr[i] = vc[row * (kHd / 8) + sch];
+#if GPBS_SEQ == 3
+    ksr[i] = ksc[row];
+    vsr[i] = vsc[row];
+#endif
   }
 
   // K row reads: row 32 kt + c, chunk 2 ks + h
@@ -128,24 +157,33 @@ __global__ __launch_bounds__(kWaves * 64) void k_prefill_attn(const u32x4* __res
     __syncthreads();  // the previous tile's reads are done
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
+#if GPBS_SEQ == 3
+      *reinterpret_cast<u32x4*>(lds + img_off(srow + 32 * i, sch)) = kv8_dequant8(kr[i], ksr[i]);
+      *reinterpret_cast<u32x4*>(lds + kTileBytes + img_off(srow + 32 * i, sch)) = kv8_dequant8(vr[i], vsr[i]);
+#else
       *reinterpret_cast<u32x4*>(lds + img_off(srow + 32 * i, sch)) = kr[i];
       *reinterpret_cast<u32x4*>(lds + kTileBytes + img_off(srow + 32 * i, sch)) = vr[i];
+#endif
     }
     __syncthreads();
     if (t + 1 < ntiles) {  // next tile in flight under this tile's MFMAs
-#if GPBS_SEQ == 2
+#if GPBS_SEQ >= 2
       const size_t pbase = head + pgn * pstride;
       if (t + 2 < ntiles) pgn = page_or0(trow[((t + 2) * kKT) >> psh], P);
 #endif
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
-#if GPBS_SEQ == 2
+#if GPBS_SEQ >= 2
         const size_t row = pbase + (min((t + 1) * kKT + srow + 32 * i, krow_last) & pmask);
 #else
         const size_t row = head + min((t + 1) * kKT + srow + 32 * i, krow_last);
 #endif
         kr[i] = kc[row * (kHd / 8) + sch];
         vr[i] = vc[row * (kHd / 8) + sch];
+#if GPBS_SEQ == 3
+        ksr[i] = ksc[row];
+        vsr[i] = vsc[row];
+#endif
       }
     }
     const int k0 = t * kKT;

@@ -64,10 +64,19 @@
 // that hold rows 0 .. pos[b] + n_b - 1 are read.  An entry outside [0, P) never
 // forms an address outside the pools: writes through it are dropped, reads
 // through it come from page 0.
+//
+// The _kv8 forms are the _paged forms over an fp8 cache (kv8_codec.hpp): e4m3
+// code pools [P, Hkv, page, hd] of one byte per element and fp32 scales
+// [P, Hkv, page], one power of two per cached row and KV head.  The write kernel
+// quantises the rows the bf16 kernel would have stored; the attention kernel
+// prefetches codes and scales and dequantises (exactly) into the same LDS images,
+// so it gives the bits of k_prefill_attn_paged over the dequantised pools.  The
+// MFMAs stay bf16.  The out-of-range rule covers all four tensors.
 #include <algorithm>
 #include <climits>
 
 #include "common.hpp"
+#include "kv8_codec.hpp"
 
 namespace gpbs_pf {
 
@@ -208,6 +217,57 @@ __global__ __launch_bounds__(256) void k_qkv_rope_cache_prefill_paged(const u32x
   }
 }
 
+// k_qkv_rope_cache_prefill_paged over an fp8 cache (kv8_codec.hpp): code pools
+// kp / vp [P, Hkv, page, 128] of one byte per element and scales ksc / vsc
+// [P, Hkv, page].  q as above.  A k row (after RoPE and the rounding of pack2,
+// the row the bf16 kernel stores) or a v row is quantised by the 16 threads that
+// hold it: 8 bytes of codes each, and thread 0 of the 16 stores the scale.
+// Threads i .. i + 15 of a row are consecutive from a multiple of 16 (256, the
+// grid stride and n8 are multiples of 16) and share (b, s, hh): they take the
+// padding and dropped-write branches together and leave the loop together, so
+// the shuffles of kv8_quant8 stay inside the group.  hd = 128 only.  Control flow and RoPE text are those of
+// the bf16 _paged kernel, so that q and the k row round as they do there.
+__global__ __launch_bounds__(256) void k_qkv_rope_cache_prefill_paged_kv8(
+    const u32x4* __restrict__ qkv, const float* __restrict__ cosb, const float* __restrict__ sinb,
+    const int* __restrict__ posb, const int* __restrict__ lenb, const int* __restrict__ table, u32x4* __restrict__ qo,
+    u32x2* __restrict__ kp, u32x2* __restrict__ vp, float* __restrict__ ksc, float* __restrict__ vsc, int B, int S,
+    int H, int Hkv, int NP, int P, int psh, int hd) {
+  const int per_head = hd / 8, heads = H + 2 * Hkv;
+  const size_t n8 = (size_t)B * S * heads * per_head;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (size_t)gridDim.x * blockDim.x) {
+    const int c = (int)(i % per_head);
+    const int hh = (int)((i / per_head) % heads);
+    const size_t bs = i / per_head / heads;
+    const int s = (int)(bs % S), b = (int)(bs / S);
+    const int pos = posb[b];
+    if (s >= seq_tokens(pos, lenb[b], S, NP << psh)) {  // padding token
+      if (hh < H) qo[(bs * H + hh) * per_head + c] = u32x4{0u, 0u, 0u, 0u};
+      continue;
+    }
+    const u32x4 v = qkv[i];
+    const int r = pos + s;
+    const int pg = table[(size_t)b * NP + (r >> psh)];
+    const bool ok = pg >= 0 && pg < P;
+    const int prow = r & ((1 << psh) - 1);
+    if (hh >= H + Hkv) {  // v: the raw row, quantised into the page row
+      if (ok) kv8_store_row(v, vp, vsc, (((size_t)pg * Hkv + (hh - H - Hkv)) << psh) + prow, c);
+      continue;
+    }
+    const float* cr = cosb + (size_t)r * (hd / 2) + c * 4;
+    const float* sr = sinb + (size_t)r * (hd / 2) + c * 4;
+    u32x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float a = bfl(v[e]), bb = bfh(v[e]), cs = cr[e], sn = sr[e];
+      o[e] = pack2(a * cs - bb * sn, a * sn + bb * cs);
+    }
+    if (hh < H)
+      qo[(bs * H + hh) * per_head + c] = o;
+    else if (ok)
+      kv8_store_row(o, kp, ksc, (((size_t)pg * Hkv + (hh - H)) << psh) + prow, c);
+  }
+}
+
 constexpr int kHd = 128;
 constexpr int kWaves = 8;
 constexpr int kRows = kWaves * 32;  // query rows (token x head of the group) per workgroup
@@ -234,6 +294,10 @@ __device__ __forceinline__ float ex2(float x) { return __builtin_amdgcn_exp2f(x)
 #undef GPBS_SEQ
 // third compilation: k_prefill_attn_paged<G>
 #define GPBS_SEQ 2
+#include "prefill_attn_body.hpp"
+#undef GPBS_SEQ
+// fourth compilation: k_prefill_attn_paged_kv8<G>
+#define GPBS_SEQ 3
 #include "prefill_attn_body.hpp"
 #undef GPBS_SEQ
 
@@ -361,6 +425,51 @@ int gpbs_hip_prefill_attn_paged(const void* q, const void* kp, const void* vp, c
     default: GPBS_PF_PAGED_LAUNCH(8); break;
   }
 #undef GPBS_PF_PAGED_LAUNCH
+  return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+// the paged entry points over an fp8 cache: e4m3 code pools kp / vp [P, Hkv, page, 128] and fp32 scales
+// ksc / vsc [P, Hkv, page]
+int gpbs_hip_qkv_rope_cache_prefill_paged_kv8(const void* qkv, const float* cosb, const float* sinb, const int* posb,
+                                              const int* lenb, const int* table, void* qo, void* kp, void* vp,
+                                              float* ksc, float* vsc, int B, int S, int H, int Hkv, int NP, int P,
+                                              int page, int hd, hipStream_t s) {
+  const int psh = page_shift(page);
+  if (!qkv || !cosb || !sinb || !posb || !lenb || !table || !qo || !kp || !vp || !ksc || !vsc || B <= 0 || S <= 0 ||
+      H <= 0 || Hkv <= 0 || NP < 1 || P < 1 || psh < 0 || hd != kHd || ((long long)NP << psh) > INT_MAX)
+    return -22;
+  const size_t n8 = (size_t)B * S * (H + 2 * Hkv) * hd / 8;
+  const int grid = (int)std::min<size_t>((n8 + 255) / 256, 8192);
+  hipLaunchKernelGGL(k_qkv_rope_cache_prefill_paged_kv8, dim3(grid), dim3(256), 0, s, (const u32x4*)qkv, cosb, sinb,
+                     posb, lenb, table, (u32x4*)qo, (u32x2*)kp, (u32x2*)vp, ksc, vsc, B, S, H, Hkv, NP, P, psh, hd);
+  return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+// out must come in zeroed: rows s >= n_b are left as they are
+int gpbs_hip_prefill_attn_paged_kv8(const void* q, const void* kp, const void* vp, const float* ksc, const float* vsc,
+                                    const int* posb, const int* lenb, const int* table, void* out, int B, int S, int H,
+                                    int Hkv, int NP, int P, int page, int hd, float scale, hipStream_t s) {
+  const int psh = page_shift(page);
+  if (!q || !kp || !vp || !ksc || !vsc || !posb || !lenb || !table || !out || hd != kHd || B <= 0 || S <= 0 ||
+      H <= 0 || Hkv <= 0 || H % Hkv || NP < 1 || P < 1 || psh < 0 || ((long long)NP << psh) > INT_MAX)
+    return -22;
+  const int G = H / Hkv;
+  if (G != 1 && G != 2 && G != 4 && G != 8) return -22;
+  const int tpw = kRows / G;
+  const long long nwg = (long long)((S + tpw - 1) / tpw) * B * Hkv;
+  if (nwg > INT_MAX) return -22;
+  const dim3 grid((unsigned)nwg), block(kWaves * 64);
+  const float sl = scale * 1.44269504088896340736f;
+#define GPBS_PF_KV8_LAUNCH(g)                                                                                  \
+  hipLaunchKernelGGL(k_prefill_attn_paged_kv8<g>, grid, block, 0, s, (const u32x4*)q, (const u32x2*)kp,       \
+                     (const u32x2*)vp, ksc, vsc, posb, lenb, table, (u32x2*)out, S, Hkv, NP, P, psh, sl, B * Hkv)
+  switch (G) {
+    case 1: GPBS_PF_KV8_LAUNCH(1); break;
+    case 2: GPBS_PF_KV8_LAUNCH(2); break;
+    case 4: GPBS_PF_KV8_LAUNCH(4); break;
+    default: GPBS_PF_KV8_LAUNCH(8); break;
+  }
+#undef GPBS_PF_KV8_LAUNCH
   return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 

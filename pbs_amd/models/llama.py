@@ -115,17 +115,22 @@ class Block(nn.Module):
         self.w2 = nn.Linear(cfg.ffn_dim, cfg.dim, bias=False)  # down
 
     def attention(self, h, cos, sin, cache=None, pos: int = 0, fused: bool = False, prefill_attn: bool = False,
-                  seq=None):
+                  seq=None, kv8: bool = False):
         B, S, _ = h.shape
         cfg, hd = self.cfg, self.cfg.head_dim
         q = self.wq(h).view(B, S, cfg.n_heads, hd)
         k = self.wk(h).view(B, S, cfg.n_kv_heads, hd)
         v = self.wv(h).view(B, S, cfg.n_kv_heads, hd)
+        if kv8:  # eager reference of the fp8 cache: v now, k after RoPE, as the kernels quantise them
+            from ..ops import llm
+            v = llm.kv8_round(v)
         if seq is not None:  # ragged eager reference: host positions / lengths per sequence
             from ..ops import llm
             pos_b, lens = seq
             kc, vc = cache
             q, k = apply_rope_seq_ref(q, cos, sin, pos_b), apply_rope_seq_ref(k, cos, sin, pos_b)
+            if kv8:
+                k = llm.kv8_round(k)
             for b in range(B):
                 n = llm.seq_tokens(pos_b[b], lens[b], S, kc.shape[2])
                 if n:
@@ -138,6 +143,8 @@ class Block(nn.Module):
         else:
             q = apply_rope_ref(q, cos[pos:pos + S], sin[pos:pos + S])
             k = apply_rope_ref(k, cos[pos:pos + S], sin[pos:pos + S])
+        if kv8:
+            k = llm.kv8_round(k)
         if cache is not None:
             kc, vc = cache
             kc[:, :, pos:pos + S] = k.transpose(1, 2)
@@ -168,7 +175,7 @@ class Block(nn.Module):
         }
 
     def forward_fp8(self, x, cos, sin, cache, pos: int, tiled: bool = False, prefill_attn: bool = False, seq=None,
-                    table=None):
+                    table=None, kv8=None):
         """Decode/prefill block on fp8 weights (fp8 MFMA linears + fused gfx950
         RMSNorm/RoPE/SwiGLU); inference only.  ``tiled``: the linears run the
         LDS-tiled fp8 GEMM (one launch for any M) where their N allows it.
@@ -178,16 +185,24 @@ class Block(nn.Module):
         form of those two launches, one position and length per sequence (any
         S; ``pos`` is not used).  ``table`` (with ``seq``): int32 [B, NP] block
         table on the device; ``cache`` is then the layer's (kpool, vpool) and the
-        two launches are the paged kernels."""
+        two launches are the paged kernels.  ``kv8`` (with ``table``): True, and
+        ``cache`` is (kpool8, vpool8, kscale, vscale) for the _kv8 kernels;
+        "emulate", and the rows the bf16 write launch stored are rounded through
+        the fp8 cache codec by torch ops before the attention launch."""
         from ..ops import llm
         cfg, hd, f = self.cfg, self.cfg.head_dim, self._fp8
         B, S, _ = x.shape
         qkv = llm.fp8_linear_q(*llm.rmsnorm_quant_fp8(x, self.attn_norm.weight, self.attn_norm.eps), f["qkv"],
                                tiled=tiled)
         nq, nkv = cfg.n_heads * hd, cfg.n_kv_heads * hd
-        kc, vc = cache
-        if seq is not None and table is not None:
+        kc, vc = cache if kv8 is not True else (None, None)
+        if kv8 is True:
+            q = llm.qkv_rope_cache_prefill_paged_kv8(qkv, cos, sin, seq[0], seq[1], table, *cache, cfg.n_heads)
+            o = llm.prefill_attn_paged_kv8(q, *cache, table, seq[0], seq[1])
+        elif seq is not None and table is not None:
             q = llm.qkv_rope_cache_prefill_paged(qkv, cos, sin, seq[0], seq[1], table, kc, vc, cfg.n_heads)
+            if kv8 == "emulate":
+                llm.kv8_emulate_rows(kc, vc, table, seq[0], seq[1], S)
             o = llm.prefill_attn_paged(q, kc, vc, table, seq[0], seq[1])
         elif seq is not None:
             q = llm.qkv_rope_cache_prefill_seq(qkv, cos, sin, seq[0], seq[1], kc, vc, cfg.n_heads)
@@ -210,7 +225,7 @@ class Block(nn.Module):
                               tiled=tiled)
         return x + llm.fp8_linear_q(*llm.swiglu_quant_fp8(gu), f["w2"], tiled=tiled)
 
-    def decode_fp8_static(self, x, cos, sin, cache, pos_i32, pos_i64, mask, pos_seq=None, table=None):
+    def decode_fp8_static(self, x, cos, sin, cache, pos_i32, pos_i64, mask, pos_seq=None, table=None, kv8=None):
         """One-token decode with every shape static and the position on device
         (capturable in a HIP graph): the KV row is written with index_copy_ at
         pos, and attention runs over the whole static cache with an additive
@@ -218,18 +233,24 @@ class Block(nn.Module):
         (int32 [B] on device, head_dim 128 only): one position per sequence,
         idle slots write nothing; pos_i32 / pos_i64 / mask are not used.
         ``table`` (with ``pos_seq``): int32 [B, NP] block table on the device;
-        ``cache`` is then the layer's (kpool, vpool) and the paged kernels run."""
+        ``cache`` is then the layer's (kpool, vpool) and the paged kernels run.
+        ``kv8`` (with ``table``): as in forward_fp8."""
         from ..ops import llm
         cfg, hd, f = self.cfg, self.cfg.head_dim, self._fp8
         B = x.shape[0]
         G = cfg.n_heads // cfg.n_kv_heads
         qkv = llm.fp8_linear_q(*llm.rmsnorm_quant_fp8(x, self.attn_norm.weight, self.attn_norm.eps), f["qkv"])
         nq, nkv = cfg.n_heads * hd, cfg.n_kv_heads * hd
-        kc, vc = cache
+        kc, vc = cache if kv8 is not True else (None, None)
         # fused gfx950 path: 2 launches between the qkv and o linears
         if pos_seq is not None or (hd == 128 and G in (1, 2, 4, 8)):
-            if pos_seq is not None and table is not None:
+            if kv8 is True:
+                q = llm.qkv_rope_cache_paged_kv8(qkv, cos, sin, pos_seq, table, *cache, cfg.n_heads)
+                o = llm.decode_attn_paged_kv8(q, *cache, table, pos_seq)
+            elif pos_seq is not None and table is not None:
                 q = llm.qkv_rope_cache_paged(qkv, cos, sin, pos_seq, table, kc, vc, cfg.n_heads)
+                if kv8 == "emulate":
+                    llm.kv8_emulate_rows(kc, vc, table, pos_seq)
                 o = llm.decode_attn_paged(q, kc, vc, table, pos_seq)
             elif pos_seq is not None:
                 q = llm.qkv_rope_cache_seq(qkv, cos, sin, pos_seq, kc, vc, cfg.n_heads)
@@ -253,9 +274,9 @@ class Block(nn.Module):
         return x + llm.fp8_linear_q(*llm.swiglu_quant_fp8(gu), f["w2"])
 
     def forward(self, x, cos, sin, cache=None, pos: int = 0, fused: bool = False, prefill_attn: bool = False,
-                seq=None):
+                seq=None, kv8: bool = False):
         if seq is not None:  # ragged: the eager reference path only
-            x = x + self.attention(self.attn_norm(x), cos, sin, cache, seq=seq)
+            x = x + self.attention(self.attn_norm(x), cos, sin, cache, seq=seq, kv8=kv8)
             h = self.mlp_norm(x)
             return x + self.w2(F.silu(self.w1(h)) * self.w3(h))
         if fused:
@@ -264,7 +285,7 @@ class Block(nn.Module):
             x = x + self.attention(h, cos, sin, cache, pos, fused=True, prefill_attn=prefill_attn)
             h = llm.rmsnorm(x, self.mlp_norm.weight, self.mlp_norm.eps)
             return x + self.w2(llm.swiglu(self.w1(h), self.w3(h)))
-        x = x + self.attention(self.attn_norm(x), cos, sin, cache, pos, prefill_attn=prefill_attn)
+        x = x + self.attention(self.attn_norm(x), cos, sin, cache, pos, prefill_attn=prefill_attn, kv8=kv8)
         h = self.mlp_norm(x)
         return x + self.w2(F.silu(self.w1(h)) * self.w3(h))
 
@@ -303,19 +324,20 @@ class Llama(nn.Module):
         return self
 
     def forward_fp8(self, tokens, cache, pos: int = 0, last_only: bool = False, tiled: bool = False,
-                    prefill_attn: bool = False, head: bool = True, seq=None, last_idx=None, table=None):
+                    prefill_attn: bool = False, head: bool = True, seq=None, last_idx=None, table=None, kv8=None):
         """``head=False`` (a non-final chunk of a chunked prefill): fill the
         caches only, no final norm / LM head; returns None.  ``seq`` = (pos_t,
         len_t) int32 [B] device tensors: a ragged batch, one position and length
         per sequence.  ``last_idx`` (long [B]): the head runs on token
         last_idx[b] of sequence b and the result is [B, 1, vocab].  ``table``
-        (with ``seq``): the block table of a paged cache, see Block.forward_fp8."""
+        (with ``seq``): the block table of a paged cache, ``kv8``: its fp8 form or
+        the emulation of it, see Block.forward_fp8."""
         from ..ops import llm
         cos, sin = self.rope(tokens.device)
         x = self.embed(tokens)
         for i, layer in enumerate(self.layers):
             x = layer.forward_fp8(x, cos, sin, cache[i], pos, tiled=tiled, prefill_attn=prefill_attn, seq=seq,
-                                  table=table)
+                                  table=table, kv8=kv8)
         if not head:
             return None
         if last_idx is not None:
@@ -325,27 +347,29 @@ class Llama(nn.Module):
         return llm.fp8_linear_q(*llm.rmsnorm_quant_fp8(x, self.norm.weight, self.norm.eps), self._fp8_head,
                                 tiled=tiled)
 
-    def decode_fp8_static(self, tok, cache, pos_i32, pos_i64, mask, pos_seq=None, table=None):
+    def decode_fp8_static(self, tok, cache, pos_i32, pos_i64, mask, pos_seq=None, table=None, kv8=None):
         from ..ops import llm
         cos, sin = self.rope(tok.device)
         x = self.embed(tok)
         for i, layer in enumerate(self.layers):
-            x = layer.decode_fp8_static(x, cos, sin, cache[i], pos_i32, pos_i64, mask, pos_seq=pos_seq, table=table)
+            x = layer.decode_fp8_static(x, cos, sin, cache[i], pos_i32, pos_i64, mask, pos_seq=pos_seq, table=table,
+                                        kv8=kv8)
         return llm.fp8_linear_q(*llm.rmsnorm_quant_fp8(x, self.norm.weight, self.norm.eps), self._fp8_head)
 
     def forward(self, tokens, cache=None, pos: int = 0, fused: bool = False, last_only: bool = False,
-                prefill_attn: bool = False, head: bool = True, seq=None, last_idx=None):
+                prefill_attn: bool = False, head: bool = True, seq=None, last_idx=None, kv8: bool = False):
         """``seq`` = (pos, lens), B host ints each: a ragged batch on the eager
         reference path (needs a cache; ``pos`` / ``fused`` are not used).
         ``last_idx`` (long [B]): the head runs on token last_idx[b] of sequence b
-        and the result is [B, 1, vocab]."""
+        and the result is [B, 1, vocab].  ``kv8`` (eager path only): every new
+        k / v row is rounded through the fp8 cache codec before it is stored."""
         cos, sin = self.rope(tokens.device)
         x = self.embed(tokens)
         for i, layer in enumerate(self.layers):
             if seq is not None:
-                x = layer(x, cos, sin, cache[i], seq=seq)
+                x = layer(x, cos, sin, cache[i], seq=seq, kv8=kv8)
             else:
-                x = layer(x, cos, sin, None if cache is None else cache[i], pos, fused, prefill_attn)
+                x = layer(x, cos, sin, None if cache is None else cache[i], pos, fused, prefill_attn, kv8=kv8)
         if not head:  # a non-final chunk of a chunked prefill: the caches are filled, no logits
             return None
         if seq is not None:
@@ -378,7 +402,7 @@ class LlamaDecoder:
     def __init__(self, cfg: LlamaConfig, batch: int, context: int, device="cuda", dtype=torch.bfloat16,
                  fused: Optional[bool] = None, fp8: bool = False, graph: bool = False, static: bool = False,
                  prefill_tiled: bool = False, prefill_attn: bool = False, ragged: bool = False,
-                 paged: bool = False, pages: Optional[int] = None, page: int = 64):
+                 paged: bool = False, pages: Optional[int] = None, page: int = 64, kv_fp8=False):
         # opt-in (implies ragged): the KV cache is a pool of `pages` pages of
         # `page` rows per layer, [pages, Hkv, page, hd], and one block table
         # [batch, ceil(context / page)] for all layers maps every slot's logical
@@ -386,6 +410,29 @@ class LlamaDecoder:
         # does not fit raises PoolExhausted, and admit(..., share=) maps the
         # full pages of another slot's prefix instead of storing them again.
         self.paged = paged
+        # opt-in (needs paged=True): the fp8 KV cache, e4m3 codes with one
+        # power-of-two fp32 scale per cached row and KV head (the codec of
+        # ops.llm.kv8_quant_ref): 132 bytes per row and KV head where bf16 stores 256.
+        #   True with fp8=True: per layer (kpool8, vpool8 float8_e4m3fn
+        #     [pages, Hkv, page, hd], kscale, vscale fp32 [pages, Hkv, page]) and the
+        #     _kv8 kernels in prefill, chunked prefill, admit(share=), the static
+        #     decode step and the captured graph; shared pages carry their scales.
+        #   "emulate" with fp8=True: bf16 pools and the bf16 paged kernels; after
+        #     every write launch torch ops on the device round exactly the rows it
+        #     wrote through the codec.  The oracle of the former; no graph.
+        #   True with fp8=False (eager, any device): every new k / v row is rounded
+        #     through the codec into pools of the model's dtype.  A numerical
+        #     reference only: it saves no memory.
+        if not (kv_fp8 is False or kv_fp8 is True or kv_fp8 == "emulate"):
+            raise ValueError(f"LlamaDecoder: kv_fp8 {kv_fp8!r} must be False, True or 'emulate'")
+        if kv_fp8 and not paged:
+            raise ValueError("LlamaDecoder: kv_fp8 needs paged=True (the fp8 cache is a paged cache)")
+        if kv_fp8 == "emulate" and not fp8:
+            raise ValueError("LlamaDecoder: kv_fp8='emulate' emulates the fp8 kernels' cache (needs fp8=True)")
+        if kv_fp8 == "emulate" and graph:
+            raise ValueError("LlamaDecoder: kv_fp8='emulate' rounds the written rows with torch ops between the "
+                             "launches and cannot be captured (graph=True)")
+        self.kv_fp8 = kv_fp8
         if paged:
             ragged = True
             if page not in (64, 128, 256):
@@ -444,9 +491,16 @@ class LlamaDecoder:
         if paged:
             self.page, self.n_table = page, -(-context // page)
             self.pool = PagePool(pages)
-            self.cache = [(torch.zeros(pages, cfg.n_kv_heads, page, hd, device=device, dtype=dtype),
-                           torch.zeros(pages, cfg.n_kv_heads, page, hd, device=device, dtype=dtype))
-                          for _ in range(cfg.n_layers)]
+            if kv_fp8 is True and fp8:  # codes and scales; a scale sits at the page index of its row
+                self.cache = [(torch.zeros(pages, cfg.n_kv_heads, page, hd, device=device, dtype=torch.float8_e4m3fn),
+                               torch.zeros(pages, cfg.n_kv_heads, page, hd, device=device, dtype=torch.float8_e4m3fn),
+                               torch.zeros(pages, cfg.n_kv_heads, page, device=device, dtype=torch.float32),
+                               torch.zeros(pages, cfg.n_kv_heads, page, device=device, dtype=torch.float32))
+                              for _ in range(cfg.n_layers)]
+            else:
+                self.cache = [(torch.zeros(pages, cfg.n_kv_heads, page, hd, device=device, dtype=dtype),
+                               torch.zeros(pages, cfg.n_kv_heads, page, hd, device=device, dtype=dtype))
+                              for _ in range(cfg.n_layers)]
             # block table: host mirror (-1 = no page) and the static device tensor the kernels read
             self._pages = [[] for _ in range(batch)]
             self._table = torch.full((batch, self.n_table), -1, dtype=torch.int32, device=device)
@@ -582,7 +636,9 @@ class LlamaDecoder:
         """One ragged forward over the paged cache: every slot (pos / lens of B
         ints), or the batch of 1 that is `slot` (one int each).  fp8: the paged
         kernels on the device table (rows of `slot` alone: a [1, NP] view).
-        Eager: gather, the dense reference path, scatter of the new rows."""
+        Eager: gather, the dense reference path, scatter of the new rows (with
+        kv_fp8 they were rounded through the codec where the path stored them, so
+        the attention of the same forward saw what the pools now hold)."""
         slots = list(range(self.batch)) if slot is None else [slot]
         dev = tokens.device
         if self.fp8:
@@ -590,14 +646,15 @@ class LlamaDecoder:
             seq = (torch.tensor(pos, dtype=torch.int32).to(dev), torch.tensor(lens, dtype=torch.int32).to(dev))
             table = self._table if slot is None else self._table[slot:slot + 1]
             return self.model.forward_fp8(tokens, self.cache, 0, last_only=True, tiled=self.prefill_tiled,
-                                          prefill_attn=True, head=head, seq=seq, last_idx=last_idx, table=table)
+                                          prefill_attn=True, head=head, seq=seq, last_idx=last_idx, table=table,
+                                          kv8=self.kv_fp8 or None)
         dense = self._dense_rows(slots, [max(p, 0) for p in pos])
         if slot is None:
             logits = self.model(tokens, cache=dense, last_only=True, head=head, seq=(list(pos), list(lens)),
-                                last_idx=last_idx)
+                                last_idx=last_idx, kv8=bool(self.kv_fp8))
         else:  # the uniform reference on the slot alone, as the dense decoder admits a request
             logits = self.model(tokens, cache=dense, pos=pos[0], fused=False, last_only=True, prefill_attn=True,
-                                head=head)
+                                head=head, kv8=bool(self.kv_fp8))
         self._scatter_rows(dense, slots, pos, [n if p >= 0 else 0 for p, n in zip(pos, lens)])
         return logits
 
@@ -785,7 +842,8 @@ class LlamaDecoder:
 
             def step():
                 logits = self.model.decode_fp8_static(self._tok, self.cache, None, None, None, pos_seq=self._pos_seq,
-                                                      table=self._table if self.paged else None)
+                                                      table=self._table if self.paged else None,
+                                                      kv8=self.kv_fp8 or None)
                 return logits[:, -1].argmax(-1, keepdim=True)
         else:
             self._pos_i32 = torch.zeros(1, dtype=torch.int32, device=dev)

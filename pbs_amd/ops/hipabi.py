@@ -110,6 +110,15 @@ def bind(lib):
        C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp)
     _p(lib, "gpbs_hip_prefill_attn_paged", C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int,
        C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp)
+    # the _paged forms over an fp8 cache: the scales (ksc, vsc: fp32 [P, Hkv, page]) follow the two code pools
+    _p(lib, "gpbs_hip_qkv_rope_cache_paged_kv8", C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int,
+       C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp)
+    _p(lib, "gpbs_hip_decode_attn_paged_kv8", C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int,
+       C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp)
+    _p(lib, "gpbs_hip_qkv_rope_cache_prefill_paged_kv8", C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int,
+       C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp)
+    _p(lib, "gpbs_hip_prefill_attn_paged_kv8", C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int,
+       C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp)
     _p(lib, "gpbs_hip_rope_bf16", C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp)
     _p(lib, "gpbs_hip_census", C.c_int, vp, C.c_int, vp, C.c_uint, C.c_uint, vp)
     _p(lib, "gpbs_hip_partition_switch", C.c_int, vp, C.c_uint, C.POINTER(C.c_uint), vp)

@@ -601,6 +601,219 @@ def attn_paged_ref(q: torch.Tensor, kpool: torch.Tensor, vpool: torch.Tensor, ta
     return attn_seq_ref(q, kc, vc, pos, lens)
 
 
+# --------------------------------------------------------------------------- fp8 paged KV cache (the _kv8 kernels)
+# The paged kernels over e4m3 pools: kpool8 / vpool8 float8_e4m3fn [P, Hkv, page, 128] and kscale / vscale fp32
+# [P, Hkv, page], one power-of-two scale per cached row and KV head; 132 bytes per row and head where bf16 stores
+# 256.  Table, page sizes, slot rules and the out-of-range rule are the paged ones: an entry outside [0, P) forms no
+# address outside any of the four tensors, its write is dropped (codes and scale), its reads come from page 0.
+#
+# The codec, for a row x[128] of finite bf16 values (inf, NaN and bf16 subnormals are outside the contract):
+#   amax = max |x|; (m, ex) = frexp(amax), m in [0.5, 1); e = ex - 9 if m <= 0.875 else ex - 8, clamped to
+#   e >= -100; e = 0 if amax == 0; scale = 2^e; code = e4m3fn(x * 2^-e), round to nearest even.
+# amax / scale lies in (224, 448], so nothing saturates; x * 2^-e is exact in fp32; float(code) * scale is exact and
+# representable in bf16, so dequantisation rounds nowhere and a kernel over the fp8 pools can be held, bit for bit,
+# to the bf16 _paged kernel over the dequantised pools.  The error per element is at most 16 * scale < amax / 14.
+# The codec is not idempotent in the scale (an amax that rounds down to 224 * scale gets half the scale on a second
+# pass): nothing may rely on requantising.
+def kv8_quant_ref(x: torch.Tensor):
+    """The fp8 KV-cache codec, plain torch on any device: x [..., 128] (any last
+    dimension) -> (codes float8_e4m3fn of x's shape, scale fp32 [...]).  The
+    exponent is taken from the bits of amax, which is frexp without a
+    transcendental on any device."""
+    xf = x.float()
+    amax = xf.abs().amax(-1)
+    bits = amax.view(torch.int32)
+    # amax = (1 + mant / 2^23) * 2^(E - 127): ex = E - 126, and m <= 0.875 iff mant <= 0.75 * 2^23
+    E, mant = bits >> 23, bits & 0x7FFFFF
+    e = (E - 126 - torch.where(mant <= 0x600000, 9, 8)).clamp(min=-100)
+    e = torch.where(amax > 0, e, torch.zeros_like(e))
+    scale = ((e + 127) << 23).to(torch.int32).view(torch.float32)
+    inv = ((127 - e) << 23).to(torch.int32).view(torch.float32)
+    return (xf * inv.unsqueeze(-1)).to(torch.float8_e4m3fn), scale
+
+
+def kv8_dequant(codes: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """float(code) * scale as bf16 (exact for what kv8_quant_ref produced)."""
+    return (codes.float() * scale.unsqueeze(-1)).to(torch.bfloat16)
+
+
+def kv8_round(x: torch.Tensor) -> torch.Tensor:
+    """x [..., hd] rounded row by row through the codec, in x's dtype: what a read
+    of the fp8 cache returns for a row written as x."""
+    return kv8_dequant(*kv8_quant_ref(x)).to(x.dtype)
+
+
+def kv8_emulate_rows(kpool: torch.Tensor, vpool: torch.Tensor, table: torch.Tensor, pos_t: torch.Tensor,
+                     len_t: Optional[torch.Tensor] = None, S: int = 1):
+    """The fp8 cache emulated on bf16 pools: after a paged write launch
+    (qkv_rope_cache_paged with len_t None, qkv_rope_cache_prefill_paged of S
+    tokens otherwise), round exactly the rows it wrote through the codec, in
+    place, with torch ops on the pools' device.  The rows are those of the paged
+    slot rule: tokens s < n_b of sequence b whose table entry lies in [0, P)."""
+    P, Hkv, page, hd = kpool.shape
+    B, NP = table.shape
+    Cl = NP * page
+    pos = pos_t.long()
+    n = torch.ones_like(pos) if len_t is None else len_t.long().clamp(max=S)
+    n = torch.where((pos >= 0) & (pos < Cl) & (n > 0), torch.minimum(n, Cl - pos), torch.zeros_like(n))
+    s = torch.arange(S, device=pos.device)
+    r = (pos[:, None] + s[None, :]).clamp(0, Cl - 1)
+    pg = torch.gather(table.long(), 1, r // page)
+    valid = (s[None, :] < n[:, None]) & (pg >= 0) & (pg < P)
+    pgv, prv = pg[valid], (r % page)[valid]
+    for pool in (kpool, vpool):
+        pool[pgv, :, prv] = kv8_round(pool[pgv, :, prv])  # [rows, Hkv, hd]
+
+
+def _need_paged_kv8(what: str, kpool8: torch.Tensor, vpool8: torch.Tensor, kscale: torch.Tensor,
+                    vscale: torch.Tensor, table: torch.Tensor):
+    """Host-side checks of the four cache tensors and the block table; returns
+    (B, NP, P, Hkv, page, hd).  As _need_paged, for the fp8 pools."""
+    if not isinstance(kpool8, torch.Tensor) or not isinstance(vpool8, torch.Tensor) or kpool8.dim() != 4 \
+            or vpool8.shape != kpool8.shape:
+        raise ValueError(f"{what}: pools {tuple(getattr(kpool8, 'shape', ()))} / "
+                         f"{tuple(getattr(vpool8, 'shape', ()))} must be [P, Hkv, page, 128] of one shape")
+    P, Hkv, page, hd = kpool8.shape
+    if page not in PAGE_SIZES or hd != 128 or P < 1 or Hkv < 1:
+        raise ValueError(f"{what}: pools {tuple(kpool8.shape)} must be [P, Hkv, page, 128] with page in {PAGE_SIZES}")
+    for name, t in (("kpool8", kpool8), ("vpool8", vpool8)):
+        if t.dtype != torch.float8_e4m3fn or not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be contiguous float8_e4m3fn, got {t.dtype} strides {t.stride()}")
+    for name, t in (("kscale", kscale), ("vscale", vscale)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (P, Hkv, page) \
+                or not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be a contiguous fp32 tensor [P, Hkv, page] = {(P, Hkv, page)}, got "
+                             f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+    if not isinstance(table, torch.Tensor) or table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] < 1:
+        raise ValueError(f"{what}: table must be an int32 tensor [B, NP >= 1], got "
+                         f"{getattr(table, 'dtype', type(table))} {tuple(getattr(table, 'shape', ()))}")
+    if not table.is_contiguous():
+        raise ValueError(f"{what}: table must be contiguous (strides {table.stride()})")
+    for name, t in (("table", table), ("kpool8", kpool8), ("vpool8", vpool8), ("kscale", kscale), ("vscale", vscale)):
+        if not t.is_cuda:
+            raise ValueError(f"{what}: {name} must be a CUDA tensor (the kernel reads it), got {t.device}")
+    return table.shape[0], table.shape[1], P, Hkv, page, hd
+
+
+def qkv_rope_cache_paged_kv8(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos_t: torch.Tensor,
+                             table: torch.Tensor, kpool8: torch.Tensor, vpool8: torch.Tensor, kscale: torch.Tensor,
+                             vscale: torch.Tensor, n_heads: int) -> torch.Tensor:
+    """qkv_rope_cache_paged over an fp8 cache: the same q; the k / v row the bf16
+    kernel would have stored goes through kv8_quant_ref into the code pools and
+    the scales, at the same page and page row."""
+    what = "qkv_rope_cache_paged_kv8"
+    B, NP, P, Hkv, page, hd = _need_paged_kv8(what, kpool8, vpool8, kscale, vscale, table)
+    Cl = NP * page
+    _need_seq(what, B, pos_t=pos_t)
+    _need(qkv, f"{what} qkv")
+    if qkv.numel() != B * (n_heads + 2 * Hkv) * hd or cos.dim() != 2 or cos.shape[-1] * 2 != hd:
+        raise ValueError(f"{what}: qkv {tuple(qkv.shape)} vs pools {tuple(kpool8.shape)}, B={B}, H={n_heads}")
+    if cos.shape[0] < Cl or sin.shape != cos.shape or cos.dtype != torch.float32 or sin.dtype != torch.float32 \
+            or not (cos.is_cuda and sin.is_cuda and cos.is_contiguous() and sin.is_contiguous()):
+        raise ValueError(f"{what}: rope tables {tuple(cos.shape)} {cos.dtype} must be contiguous fp32 CUDA tensors "
+                         f"covering NP * page = {Cl} rows")
+    q = torch.empty(B, n_heads, hd, dtype=torch.bfloat16, device=qkv.device)
+    _check(lib().gpbs_hip_qkv_rope_cache_paged_kv8(_ptr(qkv), _ptr(cos), _ptr(sin), _ptr(pos_t), _ptr(table), _ptr(q),
+                                                   _ptr(kpool8), _ptr(vpool8), _ptr(kscale), _ptr(vscale), B, n_heads,
+                                                   Hkv, NP, P, page, hd, _stream()), what)
+    return q
+
+
+def decode_attn_paged_kv8(q: torch.Tensor, kpool8: torch.Tensor, vpool8: torch.Tensor, kscale: torch.Tensor,
+                          vscale: torch.Tensor, table: torch.Tensor, pos_t: torch.Tensor,
+                          nsplit: Optional[int] = None) -> torch.Tensor:
+    """decode_attn_paged over an fp8 cache: bit-identical to decode_attn_paged on
+    the bf16 pools kv8_dequant(kpool8, kscale) / kv8_dequant(vpool8, vscale) with
+    the same nsplit (default: from (B, Hkv, Cl))."""
+    what = "decode_attn_paged_kv8"
+    B, NP, P, Hkv, page, hd = _need_paged_kv8(what, kpool8, vpool8, kscale, vscale, table)
+    Cl = NP * page
+    if q.dim() != 3 or q.shape[0] != B or q.shape[2] != hd:
+        raise ValueError(f"{what}: q {tuple(q.shape)} must be [B={B}, H, 128]")
+    H = q.shape[1]
+    if H % Hkv or (H // Hkv) not in (1, 2, 4, 8):
+        raise ValueError(f"{what}: group size H / Hkv = {H} / {Hkv} must be 1, 2, 4 or 8")
+    if q.dtype != torch.bfloat16 or not q.is_contiguous():
+        raise ValueError(f"{what}: q must be contiguous bf16, got {q.dtype} strides {q.stride()}")
+    if nsplit is not None and (not isinstance(nsplit, int) or isinstance(nsplit, bool) or nsplit < 1):
+        raise ValueError(f"{what}: nsplit={nsplit!r} must be None or an int >= 1")
+    _need_seq(what, B, pos_t=pos_t)
+    _need(q, f"{what} q")
+    out = torch.empty(B, H * hd, dtype=torch.bfloat16, device=q.device)
+    if nsplit is None:  # as decode_attn_paged
+        nsplit = max(1, min(8, -(-256 // (B * Hkv)), -(-Cl // 64)))
+    ws = torch.empty(B * Hkv * nsplit * (H // Hkv) * (hd + 2), dtype=torch.float32, device=q.device) \
+        if nsplit > 1 else None
+    _check(lib().gpbs_hip_decode_attn_paged_kv8(_ptr(q), _ptr(kpool8), _ptr(vpool8), _ptr(kscale), _ptr(vscale),
+                                                _ptr(pos_t), _ptr(table), _ptr(out), _ptr(ws), nsplit, B, H, Hkv, NP,
+                                                P, page, hd, C.c_float(hd ** -0.5), _stream()), what)
+    return out
+
+
+def qkv_rope_cache_prefill_paged_kv8(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos_t: torch.Tensor,
+                                     len_t: torch.Tensor, table: torch.Tensor, kpool8: torch.Tensor,
+                                     vpool8: torch.Tensor, kscale: torch.Tensor, vscale: torch.Tensor,
+                                     n_heads: int) -> torch.Tensor:
+    """qkv_rope_cache_prefill_paged over an fp8 cache: the same q; every k / v row
+    the bf16 kernel would have stored goes through kv8_quant_ref into the code
+    pools and the scales.  Returns q [B, S, H, hd]."""
+    what = "qkv_rope_cache_prefill_paged_kv8"
+    B, NP, P, Hkv, page, hd = _need_paged_kv8(what, kpool8, vpool8, kscale, vscale, table)
+    Cl = NP * page
+    if qkv.dim() != 3 or qkv.shape[0] != B or qkv.shape[1] < 1 or qkv.shape[2] != (n_heads + 2 * Hkv) * hd \
+            or cos.dim() != 2 or cos.shape[-1] * 2 != hd:
+        raise ValueError(f"{what}: qkv {tuple(qkv.shape)} must be [B={B}, S, (H + 2 Hkv) hd] for pools "
+                         f"{tuple(kpool8.shape)}, H={n_heads}, rope tables {tuple(cos.shape)}")
+    S = qkv.shape[1]
+    _need_seq(what, B, pos_t=pos_t, len_t=len_t)
+    if cos.shape[0] < Cl or sin.shape != cos.shape or cos.dtype != torch.float32 or sin.dtype != torch.float32 \
+            or not (cos.is_contiguous() and sin.is_contiguous()):
+        raise ValueError(f"{what}: rope tables {tuple(cos.shape)} {cos.dtype} must be contiguous fp32 and cover "
+                         f"NP * page = {Cl} rows")
+    if qkv.dtype != torch.bfloat16 or not qkv.is_contiguous():
+        raise ValueError(f"{what}: qkv must be contiguous bf16, got {qkv.dtype} strides {qkv.stride()}")
+    _need(qkv, f"{what} qkv")
+    if not (cos.is_cuda and sin.is_cuda):
+        raise ValueError(f"{what}: rope tables must be CUDA tensors")
+    q = torch.empty(B, S, n_heads, hd, dtype=torch.bfloat16, device=qkv.device)
+    _check(lib().gpbs_hip_qkv_rope_cache_prefill_paged_kv8(_ptr(qkv), _ptr(cos), _ptr(sin), _ptr(pos_t), _ptr(len_t),
+                                                           _ptr(table), _ptr(q), _ptr(kpool8), _ptr(vpool8),
+                                                           _ptr(kscale), _ptr(vscale), B, S, n_heads, Hkv, NP, P,
+                                                           page, hd, _stream()), what)
+    return q
+
+
+def prefill_attn_paged_kv8(q: torch.Tensor, kpool8: torch.Tensor, vpool8: torch.Tensor, kscale: torch.Tensor,
+                           vscale: torch.Tensor, table: torch.Tensor, pos_t: torch.Tensor,
+                           len_t: torch.Tensor) -> torch.Tensor:
+    """prefill_attn_paged over an fp8 cache: bit-identical to prefill_attn_paged
+    on the bf16 pools kv8_dequant(kpool8, kscale) / kv8_dequant(vpool8, vscale).
+    Returns [B, S, H * 128] bf16, rows s >= n_b zero."""
+    what = "prefill_attn_paged_kv8"
+    B, NP, P, Hkv, page, hd = _need_paged_kv8(what, kpool8, vpool8, kscale, vscale, table)
+    if q.dim() != 4 or q.shape[0] != B or q.shape[1] < 1 or q.shape[3] != hd:
+        raise ValueError(f"{what}: q {tuple(q.shape)} must be [B={B}, S, H, 128]")
+    S, H = q.shape[1], q.shape[2]
+    if H % Hkv or (H // Hkv) not in (1, 2, 4, 8):
+        raise ValueError(f"{what}: group size H / Hkv = {H} / {Hkv} must be 1, 2, 4 or 8")
+    if q.dtype != torch.bfloat16 or not q.is_contiguous():
+        raise ValueError(f"{what}: q must be contiguous bf16, got {q.dtype} strides {q.stride()}")
+    _need_seq(what, B, pos_t=pos_t, len_t=len_t)
+    _need(q, f"{what} q")
+    out = torch.zeros(B, S, H * hd, dtype=torch.bfloat16, device=q.device)  # the kernel stores rows < n_b only
+    _check(lib().gpbs_hip_prefill_attn_paged_kv8(_ptr(q), _ptr(kpool8), _ptr(vpool8), _ptr(kscale), _ptr(vscale),
+                                                 _ptr(pos_t), _ptr(len_t), _ptr(table), _ptr(out), B, S, H, Hkv, NP,
+                                                 P, page, hd, C.c_float(hd ** -0.5), _stream()), what)
+    return out
+
+
+def attn_paged_kv8_ref(q: torch.Tensor, kpool8: torch.Tensor, vpool8: torch.Tensor, kscale: torch.Tensor,
+                       vscale: torch.Tensor, table, pos, lens) -> torch.Tensor:
+    """Plain-torch reference of the two _kv8 attention kernels: attn_paged_ref
+    over the dequantised pools."""
+    return attn_paged_ref(q, kv8_dequant(kpool8, kscale), kv8_dequant(vpool8, vscale), table, pos, lens)
+
+
 # --------------------------------------------------------------------------- fp8 (config #5, CDNA4 fp8 MFMA)
 FP8_MAX = 448.0  # OCP e4m3fn (gfx950), not the MI300 fnuz variant
 FP8_M_TILE = 64  # rows per gpbs_hip_fp8_linear launch

@@ -28,6 +28,17 @@ _seq twin is timed in the same rounds, twice, so the rows carry its spread
 against itself.
 
     python scripts/attn_bench.py --paged [--iters 100] [--out profiles/paged_attn.jsonl]
+
+--kv8 runs instead the fp8-cache kernels against their bf16 _paged twins, with the
+--paged rows' method (B 8, 8192 rows per sequence, pages of 64 / 128 / 256 rows,
+identity and shuffled tables, lengths all 8192 and 1024..8192, prefill at S 1024):
+the bf16 pools are quantised with llm.kv8_quant_ref, the twin runs on the
+dequantised pools, and every kv8 result is checked against its twin bit for bit
+before anything is timed.  Within each of the 5 rounds the twin is timed, then the
+kv8 kernel, then the twin again, so the rows carry the twin's spread against
+itself; ratios are per round.
+
+    python scripts/attn_bench.py --kv8 [--iters 100] [--out profiles/kv8_attn.jsonl]
 """
 import argparse
 import json
@@ -271,6 +282,65 @@ def paged_rows(emit, g, iters, B=8, C=8192, pages=(64, 128, 256)):
         emit(rec)
 
 
+def kv8_rows(emit, g, iters, B=8, C=8192, pages=(64, 128, 256)):
+    i32 = dict(dtype=torch.int32, device="cuda")
+    q = torch.randn(B, H, HD, device="cuda", generator=g).bfloat16()
+    kc = torch.randn(B, HKV, C, HD, device="cuda", generator=g).bfloat16()
+    vc = torch.randn(B, HKV, C, HD, device="cuda", generator=g).bfloat16()
+    full = torch.full((B,), C - 1, **i32)
+    spread_l = [1024 + (C - 1024) * b // (B - 1) for b in range(B)]
+    spread = torch.tensor([n - 1 for n in spread_l], **i32)
+    S = 1024
+    qp = torch.randn(B, S, H, HD, device="cuda", generator=g).bfloat16()
+    zeros, all_s = torch.zeros(B, **i32), torch.full((B,), S, **i32)
+    for page in pages:
+        NP = C // page
+        for kind in ("identity", "shuffled"):
+            ids = torch.arange(B * NP, device="cuda")
+            if kind == "shuffled":
+                ids = ids[torch.randperm(B * NP, device="cuda", generator=g)]
+            table = ids.view(B, NP).to(torch.int32).contiguous()
+            four, twin = [None] * 4, []
+            for i, dense in enumerate((kc, vc)):
+                pool = torch.empty(B * NP, HKV, page, HD, device="cuda", dtype=torch.bfloat16)
+                pool[ids] = dense.view(B, HKV, NP, page, HD).permute(0, 2, 1, 3, 4).reshape(B * NP, HKV, page, HD)
+                four[i], four[2 + i] = llm.kv8_quant_ref(pool)
+                twin.append(llm.kv8_dequant(four[i], four[2 + i]))
+                del pool
+            k8, v8, ks, vs = four
+            kt, vt = twin
+            shapes = (
+                ("decode all 8192", lambda: llm.decode_attn_paged(q, kt, vt, table, full),
+                 lambda: llm.decode_attn_paged_kv8(q, k8, v8, ks, vs, table, full), None),
+                ("decode 1024..8192", lambda: llm.decode_attn_paged(q, kt, vt, table, spread),
+                 lambda: llm.decode_attn_paged_kv8(q, k8, v8, ks, vs, table, spread), {"lengths": spread_l}),
+                ("prefill all 1024", lambda: llm.prefill_attn_paged(qp, kt, vt, table, zeros, all_s),
+                 lambda: llm.prefill_attn_paged_kv8(qp, k8, v8, ks, vs, table, zeros, all_s), None))
+            for shape, twin_fn, kv8_fn, extra in shapes:
+                assert torch.equal(kv8_fn(), twin_fn()), (shape, page, kind)  # bit for bit before anything is timed
+                t = {"twin (first)": [], "kv8": [], "twin (second)": []}
+                for _ in range(ROUNDS):  # the three alternate within a round
+                    t["twin (first)"].append(timeit(twin_fn, iters))
+                    t["kv8"].append(timeit(kv8_fn, iters))
+                    t["twin (second)"].append(timeit(twin_fn, iters))
+                for k, v in t.items():
+                    kernel = ("prefill_attn_paged" if shape.startswith("prefill") else "decode_attn_paged") \
+                        + ("_kv8" if k == "kv8" else "")
+                    rec = {"bench": "kv8_attn", "name": f"{kernel} {shape.split(' ', 1)[1]}, page {page} {kind}"
+                           + ("" if k == "kv8" else f" {k[5:]}"), "kernel": kernel, "page": page, "table": kind,
+                           "B": B, "rows": C, "H": H, "Hkv": HKV, "bit_equal_to_twin": True,
+                           "us": round(med(v), 1), "us_minmax": [round(min(v), 1), round(max(v), 1)]}
+                    if k != "twin (first)":
+                        r = [a / b for a, b in zip(v, t["twin (first)"])]
+                        rec.update({"over": "twin (first)", "ratio": round(med(r), 3),
+                                    "ratio_minmax": [round(min(r), 3), round(max(r), 3)],
+                                    "ratio_rounds": [round(x, 3) for x in r]})
+                    rec.update(extra or {})
+                    emit(rec)
+            del four, twin, k8, v8, ks, vs, kt, vt
+            torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=100)
@@ -279,6 +349,7 @@ def main():
     ap.add_argument("--skip-kernel", action="store_true")
     ap.add_argument("--ragged", action="store_true", help="only the per-sequence kernels against their uniform twins")
     ap.add_argument("--paged", action="store_true", help="only the block-table kernels against their _seq twins")
+    ap.add_argument("--kv8", action="store_true", help="only the fp8-cache kernels against their bf16 _paged twins")
     a = ap.parse_args()
     out = open(a.out, "a") if a.out else None
 
@@ -294,6 +365,9 @@ def main():
         return
     if a.paged:
         paged_rows(emit, g, a.iters)
+        return
+    if a.kv8:
+        kv8_rows(emit, g, a.iters)
         return
     if not a.skip_kernel:
         kernel_row(emit, g, a.iters, 8, 1024, 0, 2048, "llm5 prompt")
