@@ -26,6 +26,14 @@ typedef unsigned short u16;
 typedef unsigned int u32;
 typedef unsigned long long u64;
 
+// bf16 pairs packed in a 32-bit word: the low / high element as fp32, and two
+// fp32 values rounded (to nearest even) into a word
+__device__ __forceinline__ float bfl(u32 w) { return __uint_as_float(w << 16); }
+__device__ __forceinline__ float bfh(u32 w) { return __uint_as_float(w & 0xffff0000u); }
+__device__ __forceinline__ u32 pack2(float lo, float hi) {
+  return (u32)__builtin_bit_cast(u16, (__bf16)lo) | ((u32)__builtin_bit_cast(u16, (__bf16)hi) << 16);
+}
+
 // Partition table shared by the scheduler (host) and tenant kernels.  Lives
 // in fine-grained pinned host memory: the dispatcher thread's store is seen
 // by the next system-scope load of a workgroup (~1-2 us over PCIe) without a

@@ -1,7 +1,7 @@
-// The decode attention kernel and its combine kernel.  Not a header of its own:
+// The decode attention kernel.  Not a header of its own:
 // decode_kernels.hip includes this text four times, inside namespace gpbs_dec, with
-// GPBS_SEQ 0 (k_decode_attn, k_decode_attn_combine: one device position for
-// the batch) and GPBS_SEQ 1 (k_decode_attn_seq, k_decode_attn_combine_seq: dpos
+// GPBS_SEQ 0 (k_decode_attn: one device position for
+// the batch) and GPBS_SEQ 1 (k_decode_attn_seq: dpos
 // is int32 [B]; sequence b has L = dpos[b] + 1 keys if 0 <= dpos[b] < C and is
 // idle otherwise: L = 0, no key loop, zero output).  Everything outside the
 // #if blocks is shared, so an active sequence gets the uniform kernel's bits.
@@ -10,8 +10,7 @@
 // (logical row r of sequence b: page table[b, r / page], page row r % page;
 // Cl = NP * page stands where C stood).  A 64-key step never straddles a page,
 // so the only new work is one wave-uniform table entry per step, loaded one
-// step ahead; an entry outside [0, P) reads page 0.  It emits no combine
-// kernel: k_decode_attn_combine_seq touches no cache and serves it as it is.
+// step ahead; an entry outside [0, P) reads page 0.
 // GPBS_SEQ 3 is a fourth compilation, k_decode_attn_paged_kv8: the paged kernel
 // over e4m3 pools (one byte per element) with one power-of-two fp32 scale per
 // (page, KV head, page row).  A lane's key row is 8 16-byte loads and its scale,
@@ -24,10 +23,8 @@
 #define GPBS_DEC_ATTN k_decode_attn_paged
 #elif GPBS_SEQ
 #define GPBS_DEC_ATTN k_decode_attn_seq
-#define GPBS_DEC_COMBINE k_decode_attn_combine_seq
 #else
 #define GPBS_DEC_ATTN k_decode_attn
-#define GPBS_DEC_COMBINE k_decode_attn_combine
 #endif
 
 // q [B, H, 128], caches [B, Hkv, C, 128], out [B, H * 128]; H = G * Hkv.
@@ -252,32 +249,5 @@ __global__ __launch_bounds__(kAttnWaves * 64) void GPBS_DEC_ATTN(const u32x4* __
   }
 }
 
-#if GPBS_SEQ < 2
-// Merge the nsplit partials of each (batch, KV head): grid B * Hkv, G * 64 threads.
-__global__ __launch_bounds__(512) void GPBS_DEC_COMBINE(const float* __restrict__ ws, u32* __restrict__ out,
-                                                             int Hkv, int G, int nsplit) {
-  const int bh = blockIdx.x, b = bh / Hkv, kvh = bh % Hkv;
-  const int g = threadIdx.x / 64, d = 2 * (threadIdx.x % 64);
-  if (g >= G) return;
-  float M = -INFINITY;
-  for (int sp = 0; sp < nsplit; ++sp) M = fmaxf(M, ws[(((size_t)bh * nsplit + sp) * G + g) * (kHd + 2) + kHd]);
-  float Ls = 0.f, a0 = 0.f, a1 = 0.f;
-  for (int sp = 0; sp < nsplit; ++sp) {
-    const float* p = ws + (((size_t)bh * nsplit + sp) * G + g) * (kHd + 2);
-    const float f = p[kHd] == -INFINITY ? 0.f : __expf(p[kHd] - M);
-    Ls += p[kHd + 1] * f;
-    a0 += p[d] * f;
-    a1 += p[d + 1] * f;
-  }
-#if GPBS_SEQ
-  const float inv = Ls == 0.f ? 0.f : 1.f / Ls;  // every partial of an idle sequence has Ls == 0
-#else
-  const float inv = 1.f / Ls;
-#endif
-  out[((size_t)b * Hkv * G + kvh * G + g) * (kHd / 2) + d / 2] = pack2(a0 * inv, a1 * inv);
-}
-#endif
-
 #undef GPBS_DEC_ATTN
-#undef GPBS_DEC_COMBINE
 

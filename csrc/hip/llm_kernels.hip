@@ -11,12 +11,6 @@
 
 namespace gpbs_hip {
 
-__device__ __forceinline__ float bfl(u32 w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float bfh(u32 w) { return __uint_as_float(w & 0xffff0000u); }
-__device__ __forceinline__ u32 pack2(float lo, float hi) {
-  return (u32)__builtin_bit_cast(u16, (__bf16)lo) | ((u32)__builtin_bit_cast(u16, (__bf16)hi) << 16);
-}
-
 constexpr int kNormThreads = 256;
 
 __global__ __launch_bounds__(kNormThreads) void k_rmsnorm_bf16(const u32x4* __restrict__ x, const u32x4* __restrict__ w,
