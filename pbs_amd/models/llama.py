@@ -397,12 +397,29 @@ def build(cfg: LlamaConfig, device, dtype) -> "Llama":
 
 
 class LlamaDecoder:
-    """Inference tenant: static KV cache, greedy decode."""
+    """Inference tenant: static KV cache; greedy decode, or with ``sampling=True``
+    temperature / top-k / top-p sampling per slot.
+
+    ``sampling=False`` (the default) picks every token with torch ``argmax``.
+    ``sampling=True`` sends every pick -- prefill in all its forms, admit, every
+    kind of decode step, the captured graph -- through the integer sampler of
+    ``pbs_amd.ops.llm`` ("token sampling"): the gfx950 kernel ``llm.sample`` with
+    fp8=True, its bit-equal torch reference ``llm.sample_ref`` on the eager paths
+    (any device).  Slots start greedy; ``set_sampling`` sets temperature, top_k,
+    top_p and seed of one slot or of all, in static device tensors the captured
+    graph reads, so a change holds from the next step on without a recapture.
+    The counter of a pick is the index its token will have in its sequence
+    (the prompt length after a prefill or admission, pos_b[b] + 1 in a decode
+    step), so a request's tokens are a function of its logits, its seed and its
+    position alone: not of the other slots, nor of how its prompt was chunked.
+    ``last_logits`` [B, V] ([1, V] after an admission) are the logits of the last
+    pick; with graph=True the static output tensor of the captured step."""
 
     def __init__(self, cfg: LlamaConfig, batch: int, context: int, device="cuda", dtype=torch.bfloat16,
                  fused: Optional[bool] = None, fp8: bool = False, graph: bool = False, static: bool = False,
                  prefill_tiled: bool = False, prefill_attn: bool = False, ragged: bool = False,
-                 paged: bool = False, pages: Optional[int] = None, page: int = 64, kv_fp8=False):
+                 paged: bool = False, pages: Optional[int] = None, page: int = 64, kv_fp8=False,
+                 sampling: bool = False):
         # opt-in (implies ragged): the KV cache is a pool of `pages` pages of
         # `page` rows per layer, [pages, Hkv, page, hd], and one block table
         # [batch, ceil(context / page)] for all layers maps every slot's logical
@@ -513,6 +530,65 @@ class LlamaDecoder:
         # the largest active position, for information only
         self.pos_b = [-1] * batch
         self.active = [False] * batch
+        # opt-in: see the class docstring.  Host mirror of the per-slot parameters (inv_temp as numpy fp32) and
+        # the static device tensors [batch] the sampler reads; every slot starts greedy.
+        self.sampling = sampling
+        self.last_logits = None
+        if sampling:
+            self._samp = {"inv_temp": [0.0] * batch, "top_k": [0] * batch, "top_p": [1.0] * batch, "seed": [0] * batch}
+            self._inv_temp = torch.zeros(batch, dtype=torch.float32, device=device)
+            self._top_k = torch.zeros(batch, dtype=torch.int32, device=device)
+            self._top_p = torch.ones(batch, dtype=torch.float32, device=device)
+            self._seed = torch.zeros(batch, dtype=torch.int64, device=device)
+
+    def set_sampling(self, slot: Optional[int] = None, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0,
+                     seed: int = 0):
+        """Sampling parameters of one slot, or of every slot (slot=None); they hold
+        from the next pick on (the captured graph reads the same tensors) and
+        survive release(): the caller sets them at admission.  temperature 0 is
+        greedy; top_k 0 (or >= vocab) and top_p 1 are off."""
+        if not self.sampling:
+            raise ValueError("LlamaDecoder: set_sampling needs sampling=True")
+        if slot is not None and (not isinstance(slot, int) or isinstance(slot, bool) or not 0 <= slot < self.batch):
+            raise ValueError(f"LlamaDecoder: slot {slot!r} of a batch of {self.batch}")
+        if isinstance(temperature, bool) or not isinstance(temperature, (int, float)) or not 0 <= temperature < math.inf:
+            raise ValueError(f"LlamaDecoder: temperature {temperature!r} must be a finite number >= 0")
+        if isinstance(top_k, bool) or not isinstance(top_k, int) or not 0 <= top_k < 2 ** 31:
+            raise ValueError(f"LlamaDecoder: top_k {top_k!r} must be an int >= 0")
+        if isinstance(top_p, bool) or not isinstance(top_p, (int, float)) or not 0 < top_p <= 1:
+            raise ValueError(f"LlamaDecoder: top_p {top_p!r} must be in (0, 1]")
+        if isinstance(seed, bool) or not isinstance(seed, int) or not -2 ** 63 <= seed < 2 ** 63:
+            raise ValueError(f"LlamaDecoder: seed {seed!r} must be an int64")
+        import numpy as np
+        with np.errstate(all="ignore"):  # an overflow is refused below
+            inv = float(np.float32(1.0) / np.float32(temperature)) if temperature else 0.0
+        if temperature and not 0 < inv < math.inf:
+            raise ValueError(f"LlamaDecoder: 1 / temperature {temperature!r} is not a finite positive fp32")
+        for b in range(self.batch) if slot is None else (slot,):
+            for name, v in (("inv_temp", inv), ("top_k", top_k), ("top_p", float(top_p)), ("seed", seed)):
+                self._samp[name][b] = v
+        self._inv_temp.copy_(torch.tensor(self._samp["inv_temp"], dtype=torch.float32))
+        self._top_k.copy_(torch.tensor(self._samp["top_k"], dtype=torch.int32))
+        self._top_p.copy_(torch.tensor(self._samp["top_p"], dtype=torch.float32))
+        self._seed.copy_(torch.tensor(self._samp["seed"], dtype=torch.int64))
+
+    def _sample(self, x: torch.Tensor, ctr_t: torch.Tensor, slot: Optional[int] = None) -> torch.Tensor:
+        """x [B, V] (slot: [1, V], that slot's parameters) and the counters int32 on x's device -> tokens [B, 1]."""
+        from ..ops import llm
+        sl = slice(None) if slot is None else slice(slot, slot + 1)
+        vec = (self._inv_temp[sl], self._top_k[sl], self._top_p[sl], self._seed[sl], ctr_t)
+        if self.fp8:  # the kernel; a missing library is an error, not a reason to run the reference
+            return llm.sample(x.contiguous(), *vec)
+        return llm.sample_ref(x, *vec)[0]
+
+    def _pick(self, logits: torch.Tensor, ctr, slot: Optional[int] = None) -> torch.Tensor:
+        """The next token of every row of logits [B, 1, V] -> [B, 1]: argmax, or with
+        sampling=True the sampler at the counters ``ctr`` (ints, -1 = idle row)."""
+        x = logits[:, -1]
+        if not self.sampling:
+            return x.argmax(-1, keepdim=True)
+        self.last_logits = x
+        return self._sample(x, torch.tensor(ctr, dtype=torch.int32).to(x.device), slot)
 
     def _forward(self, tokens, pos: int, head: bool = True, cache=None, seq=None, last_idx=None):
         """``cache``: other caches than the decoder's own (admit: the batch-1
@@ -558,7 +634,7 @@ class LlamaDecoder:
         logits = self._forward(tokens, 0)
         self.pos = tokens.shape[1]
         self._all_slots_at(self.pos)
-        return logits[:, -1].argmax(-1, keepdim=True)
+        return self._pick(logits, [self.pos] * tokens.shape[0])
 
     def _all_slots_at(self, pos: int):
         """Ragged mode, after a uniform prefill: every slot is active at the same position."""
@@ -589,7 +665,7 @@ class LlamaDecoder:
         self.pos_b = [n if n else -1 for n in lens]
         self.active = [n > 0 for n in lens]
         self._sync_pos()
-        tok = logits[:, -1].argmax(-1, keepdim=True)
+        tok = self._pick(logits, self.pos_b)  # the counter is the prompt length, -1 for an idle slot
         return tok * torch.tensor(self.active, device=dev).view(B, 1)
 
     # ------------------------------------------------------------------ paged cache
@@ -695,7 +771,7 @@ class LlamaDecoder:
         self.pos_b = [n if n else -1 for n in lens]
         self.active = [n > 0 for n in lens]
         self._sync_pos()
-        tok = logits[:, -1].argmax(-1, keepdim=True)
+        tok = self._pick(logits, self.pos_b)  # the counter is the prompt length, -1 for an idle slot
         return tok * torch.tensor(self.active, device=dev).view(B, 1)
 
     def _admit_paged(self, slot: int, tokens: torch.Tensor, chunk: int, share):
@@ -731,7 +807,7 @@ class LlamaDecoder:
             yield c1
         self.pos_b[slot], self.active[slot] = S, True
         self._sync_pos()
-        return logits[:, -1].argmax(-1, keepdim=True)
+        return self._pick(logits, [S], slot)
 
     def _grow_pages(self):
         """Before a decode step: a page for every active slot that starts one."""
@@ -784,7 +860,7 @@ class LlamaDecoder:
     def _admit_chunks(self, slot: int, tokens: torch.Tensor, chunk: int):
         # a dim-0 slice of a contiguous cache is contiguous: the uniform kernels run on it as a batch of 1
         view = [(k[slot:slot + 1], v[slot:slot + 1]) for k, v in self.cache]
-        tok = yield from self._prefill_chunks(tokens, chunk, cache=view)
+        tok = yield from self._prefill_chunks(tokens, chunk, cache=view, slot=slot)
         self.pos_b[slot], self.active[slot] = tokens.shape[1], True
         self._sync_pos()
         return tok
@@ -816,9 +892,9 @@ class LlamaDecoder:
             raise ValueError(f"LlamaDecoder: prompt of {S} tokens for a context of {self.context}")
         return self._prefill_chunks(tokens, chunk)
 
-    def _prefill_chunks(self, tokens: torch.Tensor, chunk: int, cache=None):
-        """``cache``: the batch-1 views of one slot (admit_iter); the decoder's own
-        caches, and with them every slot, otherwise."""
+    def _prefill_chunks(self, tokens: torch.Tensor, chunk: int, cache=None, slot=None):
+        """``cache``: the batch-1 views of one slot, ``slot`` (admit_iter); the
+        decoder's own caches, and with them every slot, otherwise."""
         S = tokens.shape[1]
         self.pos, logits = 0, None
         for c0 in range(0, S, chunk):
@@ -829,7 +905,7 @@ class LlamaDecoder:
             yield c1
         if cache is None:
             self._all_slots_at(S)
-        return logits[:, -1].argmax(-1, keepdim=True)
+        return self._pick(logits, [S] * tokens.shape[0], slot)
 
     def _graph_setup(self, tok: torch.Tensor):
         """Build the static-shape step; with graph=True capture it (every launch
@@ -837,6 +913,15 @@ class LlamaDecoder:
         position/token uploads."""
         dev = tok.device
         self._tok = tok.clone()
+        if self.sampling:  # the counters of the step's picks, refreshed with the positions before every step
+            self._ctr = torch.full((self.batch,), -1, dtype=torch.int32, device=dev)
+
+        def pick(logits):
+            if not self.sampling:
+                return logits[:, -1].argmax(-1, keepdim=True)
+            self._step_logits = logits[:, -1]  # under capture: the static output tensor every replay rewrites
+            return self._sample(self._step_logits, self._ctr)
+
         if self.ragged:  # one device position per sequence, refreshed from pos_b before every step
             self._pos_seq = torch.full((self.batch,), -1, dtype=torch.int32, device=dev)
 
@@ -844,7 +929,7 @@ class LlamaDecoder:
                 logits = self.model.decode_fp8_static(self._tok, self.cache, None, None, None, pos_seq=self._pos_seq,
                                                       table=self._table if self.paged else None,
                                                       kv8=self.kv_fp8 or None)
-                return logits[:, -1].argmax(-1, keepdim=True)
+                return pick(logits)
         else:
             self._pos_i32 = torch.zeros(1, dtype=torch.int32, device=dev)
             self._pos_i64 = torch.zeros(1, dtype=torch.int64, device=dev)
@@ -853,7 +938,7 @@ class LlamaDecoder:
             def step():
                 mask = torch.where(self._ar <= self._pos_i64, 0.0, float("-inf"))
                 logits = self.model.decode_fp8_static(self._tok, self.cache, self._pos_i32, self._pos_i64, mask)
-                return logits[:, -1].argmax(-1, keepdim=True)
+                return pick(logits)
 
         self._step = step
         if not self.graph:
@@ -870,6 +955,9 @@ class LlamaDecoder:
             self._out = step()
 
     def _set_pos(self):
+        if self.sampling:  # the token picked at position p has index p + 1 in its sequence
+            self._ctr.copy_(torch.tensor([p + 1 if a else -1 for p, a in zip(self.pos_b, self.active)]
+                                         if self.ragged else [self.pos + 1] * self.batch, dtype=torch.int32))
         if self.ragged:
             self._pos_seq.copy_(torch.tensor(self.pos_b, dtype=torch.int32))
             if self.paged:  # the captured graph reads the same table tensor: admission, release, growth survive
@@ -895,12 +983,14 @@ class LlamaDecoder:
                 out = self._out.clone()
             else:
                 out = self._step()
+            if self.sampling:
+                self.last_logits = self._step_logits
         elif self.paged:
             logits = self._forward_paged(tok, list(self.pos_b), [int(a) for a in self.active])
-            out = logits[:, -1].argmax(-1, keepdim=True)
+            out = self._pick(logits, [p + 1 if a else -1 for p, a in zip(self.pos_b, self.active)])
         else:
             logits = self._forward(tok, 0, seq=(list(self.pos_b), [int(a) for a in self.active]))
-            out = logits[:, -1].argmax(-1, keepdim=True)
+            out = self._pick(logits, [p + 1 if a else -1 for p, a in zip(self.pos_b, self.active)])
         self.pos_b = [p + 1 if a else -1 for p, a in zip(self.pos_b, self.active)]
         self._sync_pos()
         return out
@@ -921,6 +1011,8 @@ class LlamaDecoder:
                 out = self._out.clone()
             else:
                 out = self._step()
+            if self.sampling:
+                self.last_logits = self._step_logits
             self.pos += 1
             return out
         if self.fp8:
@@ -928,7 +1020,7 @@ class LlamaDecoder:
         else:
             logits = self.model(tok, cache=self.cache, pos=self.pos, fused=self.fused)
         self.pos += 1
-        return logits[:, -1].argmax(-1, keepdim=True)
+        return self._pick(logits, [self.pos] * tok.shape[0])
 
 
 class LlamaTrainer:

@@ -119,6 +119,8 @@ def bind(lib):
        C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp)
     _p(lib, "gpbs_hip_prefill_attn_paged_kv8", C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int,
        C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, vp)
+    # token sampling: logits, inv_temp, top_k, top_p, seed, ctr (device vectors [B]), tokens, stats, B, V, stream
+    _p(lib, "gpbs_hip_sample_rows", C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, vp)
     _p(lib, "gpbs_hip_rope_bf16", C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp)
     _p(lib, "gpbs_hip_census", C.c_int, vp, C.c_int, vp, C.c_uint, C.c_uint, vp)
     _p(lib, "gpbs_hip_partition_switch", C.c_int, vp, C.c_uint, C.POINTER(C.c_uint), vp)

@@ -1002,3 +1002,139 @@ def fp8_linear_ref(x: torch.Tensor, w: Fp8Weight) -> torch.Tensor:
     xq, sx = quant_rows_fp8_ref(x.reshape(-1, w.K))
     acc = xq.float() @ w.q.float().t()
     return (acc * sx.unsqueeze(1) * w.s.float().unsqueeze(0)).view(*x.shape[:-1], w.N)
+
+
+# --------------------------------------------------------------------------- token sampling (csrc/hip/sample_kernels.hip)
+# Temperature, top-k and top-p sampling of one token per row, defined in integers so that the kernel and the torch
+# reference agree on every token bit for bit.  One row x[V] (bf16 or fp32; -inf allowed, NaN / +inf / an all -inf row
+# are outside the contract) with inv_temp fp32 (0 = greedy; the host computes fp32(1) / fp32(T)), top_k int32 (active
+# iff 0 < top_k < V), top_p fp32 (active iff top_p < 1), seed int64 and ctr int32:
+#   idle     ctr < 0: token 0, stats 0.
+#   greedy   inv_temp == 0: the lowest index of the maximum, stats 0.
+#   weights  m = max x; y = max(((x - m) * inv_temp) * fp32(log2 e), -64), each operation one fp32 rounding;
+#            n = floor(y), f = y - n; p = 1 + f (c0 + f (c1 + ... + f c5)) in Horner steps of a separate fp32 multiply
+#            and add (no fused multiply-add); w = floor(p * 2^30) >> min(-n, 63): an integer in [0, 2^30].
+#   top-k    t = 1 (zero weights are never kept); active: t = max(1, k-th largest w); ties at t are all kept.
+#   top-p    after top-k: S_k = sum of the w >= t, P = clamp(floor(top_p * 65536), 0, 65535),
+#            target = max(1, floor(S_k * P / 65536)); t becomes the largest v whose weights >= v sum to >= target.
+#   draw     S, cnt = sum and number of the w >= t; R = 64 bits of Philox4x32-10, counter (ctr, 0, 0, 0), key (low,
+#            high word of seed), R = out[0] + 2^32 out[1]; r = floor(R * S / 2^64); the token is the smallest i whose
+#            kept weights up to and including i sum to more than r.
+#   stats    int64 (t, cnt, S, r).
+# Every sum is an integer sum, hence the same in any order over lanes, waves or workgroups.  V <= 2^20 keeps S < 2^50.
+SAMPLE_EXP2_COEF = tuple(float.fromhex(h) for h in ("0x1.62e42cp-1", "0x1.ebfd5ap-3", "0x1.c688f0p-5", "0x1.3d0c40p-7",
+                                                    "0x1.46d326p-10", "0x1.c54640p-13"))  # c0 .. c5, mirrored in the .hip
+SAMPLE_LOG2E = float.fromhex("0x1.715476p+0")  # fp32(log2 e)
+SAMPLE_MAX_V = 1 << 20
+_PHILOX_M = (0xD2511F53, 0xCD9E8D57)
+_PHILOX_W = (0x9E3779B9, 0xBB67AE85)
+
+
+def philox4x32_ref(counter, key):
+    """Philox4x32-10 on Python integers: counter 4 words, key 2 words -> 4 words."""
+    c, k = [int(v) & 0xFFFFFFFF for v in counter], [int(v) & 0xFFFFFFFF for v in key]
+    for rnd in range(10):
+        p0, p1 = _PHILOX_M[0] * c[0], _PHILOX_M[1] * c[2]
+        c = [(p1 >> 32) ^ c[1] ^ k[0], p1 & 0xFFFFFFFF, (p0 >> 32) ^ c[3] ^ k[1], p0 & 0xFFFFFFFF]
+        k = [(k[0] + _PHILOX_W[0]) & 0xFFFFFFFF, (k[1] + _PHILOX_W[1]) & 0xFFFFFFFF]
+    return c
+
+
+def sample_exp2_poly(f: torch.Tensor) -> torch.Tensor:
+    """p(f) ~ 2^f for fp32 f in [0, 1]: the Horner steps of the contract, every multiply and add a torch op of its
+    own (one fp32 rounding each)."""
+    c = [torch.tensor(v, dtype=torch.float32, device=f.device) for v in SAMPLE_EXP2_COEF]
+    p = c[5]
+    for ci in reversed(c[:5]):
+        p = f * p
+        p = p + ci
+    p = f * p
+    return p + torch.tensor(1.0, dtype=torch.float32, device=f.device)
+
+
+def sample_weights_ref(x: torch.Tensor, inv_temp: torch.Tensor) -> torch.Tensor:
+    """The integer weights of the contract: x [B, V] (bf16 / fp32), inv_temp fp32 [B] (> 0; a greedy row has no
+    weights) -> int64 [B, V] in [0, 2^30]."""
+    xf = x.float()
+    m = xf.amax(-1, keepdim=True)
+    y = (xf - m) * inv_temp.to(torch.float32).view(-1, 1)
+    y = y * torch.tensor(SAMPLE_LOG2E, dtype=torch.float32, device=x.device)
+    y = torch.clamp_min(y, -64.0)
+    n = torch.floor(y)
+    q = torch.floor(sample_exp2_poly(y - n) * float(1 << 30)).to(torch.int64)
+    return q >> (-n).to(torch.int64).clamp(max=63)
+
+
+def sample_ref(logits: torch.Tensor, inv_temp: torch.Tensor, top_k: torch.Tensor, top_p: torch.Tensor,
+               seed: torch.Tensor, ctr: torch.Tensor):
+    """Plain-torch reference of sample() on any device: logits [B, V], vectors [B] -> (tokens int64 [B, 1], stats
+    int64 [B, 4]).  Reads its vectors and the row sums on the host."""
+    if logits.dim() != 2 or logits.dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError(f"sample_ref: logits {tuple(logits.shape)} {logits.dtype} must be bf16 / fp32 [B, V]")
+    B, V = logits.shape
+    for name, t in (("inv_temp", inv_temp), ("top_k", top_k), ("top_p", top_p), ("seed", seed), ("ctr", ctr)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.numel() != B:
+            raise ValueError(f"sample_ref: {name} must be a tensor of exactly B={B} elements, got "
+                             f"{tuple(getattr(t, 'shape', ()))}")
+    if not 1 <= V <= SAMPLE_MAX_V:
+        raise ValueError(f"sample_ref: V={V} must be in [1, 2^20]")
+    dev = logits.device
+    it = inv_temp.to(device=dev, dtype=torch.float32)
+    idle, greedy = (ctr.to(dev) < 0).view(B, 1), (it == 0).view(B, 1)
+    xf = logits.float()
+    ar = torch.arange(V, device=dev)
+    first_max = torch.where(xf == xf.amax(-1, keepdim=True), ar, V).amin(-1, keepdim=True)
+    w = sample_weights_ref(logits, torch.where(it == 0, torch.ones_like(it), it))
+    ws = w.sort(-1, descending=True).values
+    k = top_k.to(dev).long().view(B, 1)
+    k_on = (k > 0) & (k < V)
+    t = torch.where(k_on, ws.gather(1, (k - 1).clamp(0, V - 1)), 1).clamp(min=1)
+    s_k = (w * (w >= t)).sum(-1, keepdim=True)
+    tp = top_p.to(device=dev, dtype=torch.float32).view(B, 1)
+    P = torch.floor(tp * 65536.0).clamp(0, 65535).to(torch.int64)
+    target = ((s_k >> 16) * P + (((s_k & 0xFFFF) * P) >> 16)).clamp(min=1)
+    j = torch.searchsorted(ws.cumsum(-1), target).clamp(max=V - 1)  # first j whose descending prefix sum reaches target
+    t = torch.where(tp < 1, ws.gather(1, j), t)
+    kept = w * (w >= t)
+    S, cnt = kept.sum(-1), (w >= t).sum(-1)
+    r = []
+    for b, (s_b, seed_b, ctr_b) in enumerate(zip(S.tolist(), seed.tolist(), ctr.tolist())):
+        seed_b &= 0xFFFFFFFFFFFFFFFF
+        out = philox4x32_ref((max(ctr_b, 0), 0, 0, 0), (seed_b & 0xFFFFFFFF, seed_b >> 32))
+        r.append(((out[0] + (out[1] << 32)) * s_b) >> 64)
+    r = torch.tensor(r, dtype=torch.int64, device=dev).view(B, 1)
+    tok = torch.searchsorted(kept.cumsum(-1), r, right=True).clamp(max=V - 1)
+    tok = torch.where(greedy, first_max, tok)
+    stats = torch.cat([t, cnt.view(B, 1), S.view(B, 1), r], 1)
+    off = idle | greedy
+    return torch.where(idle, torch.zeros_like(tok), tok), torch.where(off, torch.zeros_like(stats), stats)
+
+
+def sample(logits: torch.Tensor, inv_temp: torch.Tensor, top_k: torch.Tensor, top_p: torch.Tensor,
+           seed: torch.Tensor, ctr: torch.Tensor, stats: bool = False):
+    """One token per row by the contract above (k_sample_rows, one workgroup per row): logits bf16 [B, V] with
+    V % 8 == 0 and 8 <= V <= 2^20; inv_temp / top_p fp32 [B], top_k / ctr int32 [B], seed int64 [B], all on the
+    GPU.  The kernel reads the five vectors at run time (valid inside a captured graph, which then follows their
+    values); only the host side of them is checked.  Returns tokens int64 [B, 1], with stats=True also the int64
+    [B, 4] rows (t, cnt, S, r).  Bit-equal to sample_ref."""
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 2:
+        raise ValueError(f"sample: logits must be [B, V], got {tuple(getattr(logits, 'shape', ()))}")
+    _need(logits, "sample logits")
+    B, V = logits.shape
+    if B < 1 or V % 8 or not 8 <= V <= SAMPLE_MAX_V:
+        raise ValueError(f"sample: logits {tuple(logits.shape)} need B >= 1, V % 8 == 0 and 8 <= V <= 2^20")
+    for name, t, dt in (("inv_temp", inv_temp, torch.float32), ("top_k", top_k, torch.int32),
+                        ("top_p", top_p, torch.float32), ("seed", seed, torch.int64), ("ctr", ctr, torch.int32)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 1 or t.numel() != B:
+            raise ValueError(f"sample: {name} must be a {dt} tensor of exactly B={B} elements, got "
+                             f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+        if not t.is_contiguous():
+            raise ValueError(f"sample: {name} must be contiguous (strides {t.stride()})")
+        if not t.is_cuda or t.device != logits.device:
+            raise ValueError(f"sample: {name} must be on the logits' device {logits.device} (the kernel reads it), "
+                             f"got {t.device}")
+    tok = torch.empty(B, 1, dtype=torch.int64, device=logits.device)
+    st = torch.empty(B, 4, dtype=torch.int64, device=logits.device)
+    _check(lib().gpbs_hip_sample_rows(_ptr(logits), _ptr(inv_temp), _ptr(top_k), _ptr(top_p), _ptr(seed), _ptr(ctr),
+                                      _ptr(tok), _ptr(st), B, V, _stream()), "sample_rows")
+    return (tok, st) if stats else tok
