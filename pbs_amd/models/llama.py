@@ -174,43 +174,26 @@ class Block(nn.Module):
             "w2": llm.Fp8Weight(self.w2.weight),
         }
 
-    def forward_fp8(self, x, cos, sin, cache, pos: int, tiled: bool = False, prefill_attn: bool = False, seq=None,
-                    table=None, kv8=None):
+    def forward_fp8(self, x, cos, sin, cache, pos: int, tiled: bool = False, view=None):
         """Decode/prefill block on fp8 weights (fp8 MFMA linears + fused gfx950
         RMSNorm/RoPE/SwiGLU); inference only.  ``tiled``: the linears run the
         LDS-tiled fp8 GEMM (one launch for any M) where their N allows it.
-        ``prefill_attn``: for S > 1 the attention block is two gfx950 launches
-        (qkv_rope_cache_prefill, prefill_attn) instead of RoPE, cache copies and
-        SDPA.  ``seq`` = (pos_t, len_t), int32 [B] device tensors: the ragged
-        form of those two launches, one position and length per sequence (any
-        S; ``pos`` is not used).  ``table`` (with ``seq``): int32 [B, NP] block
-        table on the device; ``cache`` is then the layer's (kpool, vpool) and the
-        two launches are the paged kernels.  ``kv8`` (with ``table``): True, and
-        ``cache`` is (kpool8, vpool8, kscale, vscale) for the _kv8 kernels;
-        "emulate", and the rows the bf16 write launch stored are rounded through
-        the fp8 cache codec by torch ops before the attention launch."""
+        ``view``: this layer's cache view (ops.llm: DenseUniform, DenseSeq,
+        Paged, ...); the attention block is then two gfx950 launches, write and
+        attend, in the view's form, and ``cache`` / ``pos`` are not used.
+        Without one: RoPE, cache copies and SDPA on ``cache`` = (kc, vc).  The
+        choice is the caller's: Llama.forward_fp8 builds the uniform view for
+        prefill_attn, this method never does."""
         from ..ops import llm
         cfg, hd, f = self.cfg, self.cfg.head_dim, self._fp8
         B, S, _ = x.shape
         qkv = llm.fp8_linear_q(*llm.rmsnorm_quant_fp8(x, self.attn_norm.weight, self.attn_norm.eps), f["qkv"],
                                tiled=tiled)
         nq, nkv = cfg.n_heads * hd, cfg.n_kv_heads * hd
-        kc, vc = cache if kv8 is not True else (None, None)
-        if kv8 is True:
-            q = llm.qkv_rope_cache_prefill_paged_kv8(qkv, cos, sin, seq[0], seq[1], table, *cache, cfg.n_heads)
-            o = llm.prefill_attn_paged_kv8(q, *cache, table, seq[0], seq[1])
-        elif seq is not None and table is not None:
-            q = llm.qkv_rope_cache_prefill_paged(qkv, cos, sin, seq[0], seq[1], table, kc, vc, cfg.n_heads)
-            if kv8 == "emulate":
-                llm.kv8_emulate_rows(kc, vc, table, seq[0], seq[1], S)
-            o = llm.prefill_attn_paged(q, kc, vc, table, seq[0], seq[1])
-        elif seq is not None:
-            q = llm.qkv_rope_cache_prefill_seq(qkv, cos, sin, seq[0], seq[1], kc, vc, cfg.n_heads)
-            o = llm.prefill_attn_seq(q, kc, vc, seq[0], seq[1])
-        elif prefill_attn and S > 1:
-            q = llm.qkv_rope_cache_prefill(qkv, cos, sin, pos, kc, vc, cfg.n_heads)
-            o = llm.prefill_attn(q, kc, vc, pos)
+        if view is not None:
+            o = llm.attend_prefill(view, llm.write_prefill(view, qkv, cos, sin, cfg.n_heads))
         else:
+            kc, vc = cache
             q = qkv[..., :nq].reshape(B, S, cfg.n_heads, hd)
             k = qkv[..., nq:nq + nkv].reshape(B, S, cfg.n_kv_heads, hd)
             v = qkv[..., nq + nkv:].reshape(B, S, cfg.n_kv_heads, hd)
@@ -225,42 +208,29 @@ class Block(nn.Module):
                               tiled=tiled)
         return x + llm.fp8_linear_q(*llm.swiglu_quant_fp8(gu), f["w2"], tiled=tiled)
 
-    def decode_fp8_static(self, x, cos, sin, cache, pos_i32, pos_i64, mask, pos_seq=None, table=None, kv8=None):
+    def decode_fp8_static(self, x, cos, sin, cache, pos_i32, pos_i64, mask, view=None):
         """One-token decode with every shape static and the position on device
-        (capturable in a HIP graph): the KV row is written with index_copy_ at
-        pos, and attention runs over the whole static cache with an additive
-        mask, grouped per KV head (GQA without repeating K/V).  ``pos_seq``
-        (int32 [B] on device, head_dim 128 only): one position per sequence,
-        idle slots write nothing; pos_i32 / pos_i64 / mask are not used.
-        ``table`` (with ``pos_seq``): int32 [B, NP] block table on the device;
-        ``cache`` is then the layer's (kpool, vpool) and the paged kernels run.
-        ``kv8`` (with ``table``): as in forward_fp8."""
+        (capturable in a HIP graph).  ``view``: this layer's cache view (as in
+        forward_fp8, whose position tensors the captured graph keeps reading):
+        two gfx950 launches, write and attend, between the qkv and o linears;
+        ``cache`` and the three position arguments are not used.  Without one:
+        the KV row is written with index_copy_ at pos, and attention runs over
+        the whole static cache with an additive mask, grouped per KV head (GQA
+        without repeating K/V), for any head geometry.  The choice is the
+        caller's: Llama.decode_fp8_static builds the uniform view where the
+        kernels take the geometry (head_dim 128), this method never does."""
         from ..ops import llm
         cfg, hd, f = self.cfg, self.cfg.head_dim, self._fp8
         B = x.shape[0]
         G = cfg.n_heads // cfg.n_kv_heads
         qkv = llm.fp8_linear_q(*llm.rmsnorm_quant_fp8(x, self.attn_norm.weight, self.attn_norm.eps), f["qkv"])
         nq, nkv = cfg.n_heads * hd, cfg.n_kv_heads * hd
-        kc, vc = cache if kv8 is not True else (None, None)
-        # fused gfx950 path: 2 launches between the qkv and o linears
-        if pos_seq is not None or (hd == 128 and G in (1, 2, 4, 8)):
-            if kv8 is True:
-                q = llm.qkv_rope_cache_paged_kv8(qkv, cos, sin, pos_seq, table, *cache, cfg.n_heads)
-                o = llm.decode_attn_paged_kv8(q, *cache, table, pos_seq)
-            elif pos_seq is not None and table is not None:
-                q = llm.qkv_rope_cache_paged(qkv, cos, sin, pos_seq, table, kc, vc, cfg.n_heads)
-                if kv8 == "emulate":
-                    llm.kv8_emulate_rows(kc, vc, table, pos_seq)
-                o = llm.decode_attn_paged(q, kc, vc, table, pos_seq)
-            elif pos_seq is not None:
-                q = llm.qkv_rope_cache_seq(qkv, cos, sin, pos_seq, kc, vc, cfg.n_heads)
-                o = llm.decode_attn_seq(q, kc, vc, pos_seq)
-            else:
-                q = llm.qkv_rope_cache(qkv, cos, sin, pos_i32, kc, vc, cfg.n_heads)
-                o = llm.decode_attn(q, kc, vc, pos_i32)
+        if view is not None:
+            o = llm.attend_decode(view, llm.write_decode(view, qkv, cos, sin, cfg.n_heads))
             x = llm.fp8_linear_q(*llm.quant_rows_fp8(o.view(B, 1, nq)), f["o"], resid=x)
             gu = llm.fp8_linear_q(*llm.rmsnorm_quant_fp8(x, self.mlp_norm.weight, self.mlp_norm.eps), f["w13"])
             return llm.fp8_linear_q(*llm.swiglu_quant_fp8(gu), f["w2"], resid=x)
+        kc, vc = cache
         q = llm.rope_dpos(qkv[..., :nq].reshape(B, 1, cfg.n_heads, hd), cos, sin, pos_i32)
         k = llm.rope_dpos(qkv[..., nq:nq + nkv].reshape(B, 1, cfg.n_kv_heads, hd), cos, sin, pos_i32)
         v = qkv[..., nq + nkv:].reshape(B, 1, cfg.n_kv_heads, hd)
@@ -324,20 +294,20 @@ class Llama(nn.Module):
         return self
 
     def forward_fp8(self, tokens, cache, pos: int = 0, last_only: bool = False, tiled: bool = False,
-                    prefill_attn: bool = False, head: bool = True, seq=None, last_idx=None, table=None, kv8=None):
+                    prefill_attn: bool = False, head: bool = True, last_idx=None, views=None):
         """``head=False`` (a non-final chunk of a chunked prefill): fill the
-        caches only, no final norm / LM head; returns None.  ``seq`` = (pos_t,
-        len_t) int32 [B] device tensors: a ragged batch, one position and length
-        per sequence.  ``last_idx`` (long [B]): the head runs on token
-        last_idx[b] of sequence b and the result is [B, 1, vocab].  ``table``
-        (with ``seq``): the block table of a paged cache, ``kv8``: its fp8 form or
-        the emulation of it, see Block.forward_fp8."""
+        caches only, no final norm / LM head; returns None.  ``last_idx`` (long
+        [B]): the head runs on token last_idx[b] of sequence b and the result is
+        [B, 1, vocab].  ``views``: one cache view per layer, see
+        Block.forward_fp8 (``cache`` / ``pos`` are then not used); without them
+        ``prefill_attn`` with S > 1 is the uniform view of ``cache`` at ``pos``."""
         from ..ops import llm
         cos, sin = self.rope(tokens.device)
         x = self.embed(tokens)
+        if views is None and prefill_attn and tokens.shape[1] > 1:
+            views = [llm.DenseUniform(kc, vc, pos) for kc, vc in cache]
         for i, layer in enumerate(self.layers):
-            x = layer.forward_fp8(x, cos, sin, cache[i], pos, tiled=tiled, prefill_attn=prefill_attn, seq=seq,
-                                  table=table, kv8=kv8)
+            x = layer.forward_fp8(x, cos, sin, cache[i], pos, tiled=tiled, view=None if views is None else views[i])
         if not head:
             return None
         if last_idx is not None:
@@ -347,13 +317,19 @@ class Llama(nn.Module):
         return llm.fp8_linear_q(*llm.rmsnorm_quant_fp8(x, self.norm.weight, self.norm.eps), self._fp8_head,
                                 tiled=tiled)
 
-    def decode_fp8_static(self, tok, cache, pos_i32, pos_i64, mask, pos_seq=None, table=None, kv8=None):
+    def decode_fp8_static(self, tok, cache, pos_i32=None, pos_i64=None, mask=None, views=None):
+        """``views``: one cache view per layer, see Block.decode_fp8_static; without
+        them the uniform view of ``cache`` at ``pos_i32`` where the kernels take
+        the model's head geometry, the index_copy_ + mask step where not."""
         from ..ops import llm
+        cfg = self.cfg
         cos, sin = self.rope(tok.device)
         x = self.embed(tok)
+        if views is None and cfg.head_dim == 128 and cfg.n_heads // cfg.n_kv_heads in (1, 2, 4, 8):
+            views = [llm.DenseUniform(kc, vc, pos_i32) for kc, vc in cache]
         for i, layer in enumerate(self.layers):
-            x = layer.decode_fp8_static(x, cos, sin, cache[i], pos_i32, pos_i64, mask, pos_seq=pos_seq, table=table,
-                                        kv8=kv8)
+            x = layer.decode_fp8_static(x, cos, sin, cache[i], pos_i32, pos_i64, mask,
+                                        view=None if views is None else views[i])
         return llm.fp8_linear_q(*llm.rmsnorm_quant_fp8(x, self.norm.weight, self.norm.eps), self._fp8_head)
 
     def forward(self, tokens, cache=None, pos: int = 0, fused: bool = False, last_only: bool = False,
@@ -464,10 +440,13 @@ class LlamaDecoder:
         # and a new request admitted into its slot while the others keep
         # decoding.  fp8=True runs the per-sequence gfx950 kernels; fp8=False is
         # the eager reference on any device and dtype.  No sliding window.
+        # The ragged kernels, and those of prefill_attn below (which ragged implies), take one head geometry.
         G = cfg.n_heads // cfg.n_kv_heads
-        if ragged and (cfg.head_dim != 128 or cfg.n_heads % cfg.n_kv_heads or G not in (1, 2, 4, 8)):
-            raise ValueError(f"LlamaDecoder: ragged needs head_dim 128 and n_heads / n_kv_heads in 1/2/4/8, "
-                             f"got head_dim {cfg.head_dim}, {cfg.n_heads} / {cfg.n_kv_heads} heads")
+        if (ragged or prefill_attn) and (cfg.head_dim != 128 or cfg.n_heads % cfg.n_kv_heads
+                                         or G not in (1, 2, 4, 8)):
+            raise ValueError(f"LlamaDecoder: {'ragged' if ragged else 'prefill_attn'} needs head_dim 128 and "
+                             f"n_heads / n_kv_heads in 1/2/4/8, got head_dim {cfg.head_dim}, {cfg.n_heads} / "
+                             f"{cfg.n_kv_heads} heads")
         if ragged and fused and not fp8:
             raise ValueError("LlamaDecoder: ragged=True runs on the fp8 kernels (fp8=True) or the eager reference "
                              "(fused=False); there is no fused bf16 ragged path")
@@ -478,6 +457,11 @@ class LlamaDecoder:
                 fused = False
             else:
                 static = True  # every ragged decode step is the static-shape step
+        # opt-in: calls with S > 1 run causal GQA attention offset by the cache
+        # position (the gfx950 MFMA kernel on the fused / fp8 paths, its torch
+        # reference on the eager path), which is what lets a prompt be prefilled
+        # in chunks; S == 1 steps and the static / graph decode are untouched
+        self.prefill_attn = prefill_attn
         self.cfg, self.batch, self.context = cfg, batch, context
         self.model = build(cfg, device, dtype)
         self.model.eval()
@@ -487,15 +471,6 @@ class LlamaDecoder:
         # GEMM (one launch per linear) instead of one weight-streaming launch
         # per 64 rows; decode steps are untouched
         self.prefill_tiled = prefill_tiled
-        # opt-in: calls with S > 1 run causal GQA attention offset by the cache
-        # position (the gfx950 MFMA kernel on the fused / fp8 paths, its torch
-        # reference on the eager path), which is what lets a prompt be prefilled
-        # in chunks; S == 1 steps and the static / graph decode are untouched
-        G = cfg.n_heads // cfg.n_kv_heads
-        if prefill_attn and (cfg.head_dim != 128 or cfg.n_heads % cfg.n_kv_heads or G not in (1, 2, 4, 8)):
-            raise ValueError(f"LlamaDecoder: prefill_attn needs head_dim 128 and n_heads / n_kv_heads in 1/2/4/8, "
-                             f"got head_dim {cfg.head_dim}, {cfg.n_heads} / {cfg.n_kv_heads} heads")
-        self.prefill_attn = prefill_attn
         if fp8:  # weights streamed as e4m3fn through the fp8 MFMA linears (half the bytes of bf16)
             with torch.no_grad():
                 self.model.attach_fp8()
@@ -592,14 +567,29 @@ class LlamaDecoder:
 
     def _forward(self, tokens, pos: int, head: bool = True, cache=None, seq=None, last_idx=None):
         """``cache``: other caches than the decoder's own (admit: the batch-1
-        views of one slot).  ``seq`` / ``last_idx``: a ragged batch, see
-        Llama.forward / forward_fp8."""
+        views of one slot).  ``seq`` = (pos, lens), B ints each, and
+        ``last_idx``: a ragged batch over the decoder's own caches."""
         cache = self.cache if cache is None else cache
         if self.fp8:
             return self.model.forward_fp8(tokens, cache, pos, last_only=True, tiled=self.prefill_tiled,
-                                          prefill_attn=self.prefill_attn, head=head, seq=seq, last_idx=last_idx)
+                                          prefill_attn=self.prefill_attn, head=head, last_idx=last_idx,
+                                          views=None if seq is None else self._views(tokens.device, *seq))
         return self.model(tokens, cache=cache, pos=pos, fused=self.fused, last_only=True,
                           prefill_attn=self.prefill_attn, head=head, seq=seq, last_idx=last_idx)
+
+    def _views(self, dev, pos, lens, table=None):
+        """One cache view (ops.llm) per layer for a ragged prefill forward on the
+        fp8 kernels, in the form of the decoder's mode: pos / lens (B ints each)
+        are uploaded once and every layer's view reads the same two tensors."""
+        pos_t, len_t = torch.tensor(pos, dtype=torch.int32).to(dev), torch.tensor(lens, dtype=torch.int32).to(dev)
+        return self._layer_views(pos_t, len_t, table)
+
+    def _layer_views(self, pos_t, len_t=None, table=None):
+        from ..ops import llm
+        if not self.paged:
+            return [llm.DenseSeq(kc, vc, pos_t, len_t) for kc, vc in self.cache]
+        form = {False: llm.Paged, True: llm.PagedKv8, "emulate": llm.PagedEmulated}[self.kv_fp8]
+        return [form(*c, table, pos_t, len_t) for c in self.cache]
 
     @staticmethod
     def _drain(it):
@@ -624,10 +614,7 @@ class LlamaDecoder:
         if lens is not None:
             if not self.ragged:
                 raise ValueError("LlamaDecoder: lens needs ragged=True")
-            if chunk is not None:
-                raise ValueError("LlamaDecoder: lens with chunk is not supported (a ragged prefill is one launch per "
-                                 "layer; admit_iter chunks one request)")
-            return self._prefill_ragged(tokens, lens)
+            return self._prefill_ragged(tokens, self._lens(tokens, lens, chunk))
         if chunk is not None:
             return self._drain(self.prefill_iter(tokens, chunk))
         self.pos = 0
@@ -645,23 +632,33 @@ class LlamaDecoder:
     def _sync_pos(self):
         self.pos = max((p for p, a in zip(self.pos_b, self.active) if a), default=0)
 
-    def _prefill_ragged(self, tokens: torch.Tensor, lens) -> torch.Tensor:
+    def _lens(self, tokens: torch.Tensor, lens, chunk) -> list:
+        """The prompt lengths of a ragged prefill as B ints; None: every prompt is
+        all of tokens [B, S], the one form that may run in chunks."""
         B, S = tokens.shape
-        lens = [int(n) for n in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
+        if lens is not None and chunk is not None:
+            raise ValueError("LlamaDecoder: lens with chunk is not supported (a ragged prefill is one launch per "
+                             "layer; admit_iter chunks one request)")
+        if isinstance(lens, torch.Tensor):
+            lens = lens.tolist()
+        lens = [S] * B if lens is None else [int(n) for n in lens]
         if B != self.batch or len(lens) != B or any(n < 0 or n > S for n in lens):
             raise ValueError(f"LlamaDecoder: lens {lens} for tokens {tuple(tokens.shape)} and a batch of {self.batch} "
                              f"(one length in [0, S] per slot)")
         if max(lens) > self.context:
             raise ValueError(f"LlamaDecoder: prompt of {max(lens)} tokens for a context of {self.context}")
-        dev = tokens.device
-        pos = [0 if n else -1 for n in lens]
-        if self.fp8:
-            seq = (torch.tensor(pos, dtype=torch.int32).to(dev), torch.tensor(lens, dtype=torch.int32).to(dev))
-        else:
-            seq = (pos, lens)
+        return lens
+
+    @staticmethod
+    def _chunk(chunk):
+        if not isinstance(chunk, int) or isinstance(chunk, bool) or chunk < 1:
+            raise ValueError(f"LlamaDecoder: chunk must be a positive int, got {chunk!r}")
+
+    def _prefill_ragged(self, tokens: torch.Tensor, lens) -> torch.Tensor:
+        B, dev = tokens.shape[0], tokens.device
         last = torch.tensor([max(n - 1, 0) for n in lens], device=dev)
         self.pos_b, self.active = [-1] * B, [False] * B
-        logits = self._forward(tokens, 0, seq=seq, last_idx=last)
+        logits = self._forward(tokens, 0, seq=([0 if n else -1 for n in lens], lens), last_idx=last)
         self.pos_b = [n if n else -1 for n in lens]
         self.active = [n > 0 for n in lens]
         self._sync_pos()
@@ -719,11 +716,9 @@ class LlamaDecoder:
         dev = tokens.device
         if self.fp8:
             self._sync_table()
-            seq = (torch.tensor(pos, dtype=torch.int32).to(dev), torch.tensor(lens, dtype=torch.int32).to(dev))
-            table = self._table if slot is None else self._table[slot:slot + 1]
-            return self.model.forward_fp8(tokens, self.cache, 0, last_only=True, tiled=self.prefill_tiled,
-                                          prefill_attn=True, head=head, seq=seq, last_idx=last_idx, table=table,
-                                          kv8=self.kv_fp8 or None)
+            views = self._views(dev, pos, lens, self._table if slot is None else self._table[slot:slot + 1])
+            return self.model.forward_fp8(tokens, self.cache, 0, last_only=True, tiled=self.prefill_tiled, head=head,
+                                          last_idx=last_idx, views=views)
         dense = self._dense_rows(slots, [max(p, 0) for p in pos])
         if slot is None:
             logits = self.model(tokens, cache=dense, last_only=True, head=head, seq=(list(pos), list(lens)),
@@ -736,19 +731,9 @@ class LlamaDecoder:
 
     def _prefill_paged(self, tokens: torch.Tensor, chunk, lens) -> torch.Tensor:
         B, S = tokens.shape
-        if lens is not None and chunk is not None:
-            raise ValueError("LlamaDecoder: lens with chunk is not supported (a ragged prefill is one launch per "
-                             "layer; admit_iter chunks one request)")
-        if lens is None:
-            lens = [S] * B
-        lens = [int(n) for n in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
-        if B != self.batch or len(lens) != B or any(n < 0 or n > S for n in lens):
-            raise ValueError(f"LlamaDecoder: lens {lens} for tokens {tuple(tokens.shape)} and a batch of {self.batch} "
-                             f"(one length in [0, S] per slot)")
-        if max(lens) > self.context:
-            raise ValueError(f"LlamaDecoder: prompt of {max(lens)} tokens for a context of {self.context}")
-        if chunk is not None and (not isinstance(chunk, int) or isinstance(chunk, bool) or chunk < 1):
-            raise ValueError(f"LlamaDecoder: chunk must be a positive int, got {chunk!r}")
+        lens = self._lens(tokens, lens, chunk)
+        if chunk is not None:
+            self._chunk(chunk)
         # every slot is reset: its pages go back first, and come back if the new prompts do not fit
         snap, held = self.pool.snapshot(), [list(ids) for ids in self._pages]
         try:
@@ -847,8 +832,7 @@ class LlamaDecoder:
             raise ValueError(f"LlamaDecoder: slot {slot!r} of a batch of {self.batch}")
         if self.active[slot]:
             raise ValueError(f"LlamaDecoder: slot {slot} is active (at position {self.pos_b[slot]}); release it first")
-        if not isinstance(chunk, int) or isinstance(chunk, bool) or chunk < 1:
-            raise ValueError(f"LlamaDecoder: chunk must be a positive int, got {chunk!r}")
+        self._chunk(chunk)
         tokens = tokens.view(1, -1)
         S = tokens.shape[1]
         if not 0 < S <= self.context:
@@ -885,8 +869,7 @@ class LlamaDecoder:
         if not self.prefill_attn:
             raise ValueError("LlamaDecoder: chunked prefill needs prefill_attn=True (SDPA's is_causal mask is "
                              "top-left aligned, wrong for a chunk at pos > 0)")
-        if not isinstance(chunk, int) or isinstance(chunk, bool) or chunk < 1:
-            raise ValueError(f"LlamaDecoder: chunk must be a positive int, got {chunk!r}")
+        self._chunk(chunk)
         S = tokens.shape[1]
         if not 0 < S <= self.context:
             raise ValueError(f"LlamaDecoder: prompt of {S} tokens for a context of {self.context}")
@@ -924,12 +907,11 @@ class LlamaDecoder:
 
         if self.ragged:  # one device position per sequence, refreshed from pos_b before every step
             self._pos_seq = torch.full((self.batch,), -1, dtype=torch.int32, device=dev)
+            # built once: every step, and the captured graph, reads these position, table and cache tensors
+            views = self._layer_views(self._pos_seq, table=self._table if self.paged else None)
 
             def step():
-                logits = self.model.decode_fp8_static(self._tok, self.cache, None, None, None, pos_seq=self._pos_seq,
-                                                      table=self._table if self.paged else None,
-                                                      kv8=self.kv_fp8 or None)
-                return pick(logits)
+                return pick(self.model.decode_fp8_static(self._tok, self.cache, views=views))
         else:
             self._pos_i32 = torch.zeros(1, dtype=torch.int32, device=dev)
             self._pos_i64 = torch.zeros(1, dtype=torch.int64, device=dev)
@@ -966,6 +948,23 @@ class LlamaDecoder:
         self._pos_i32.fill_(self.pos)
         self._pos_i64.fill_(self.pos)
 
+    def _static_step(self, tok: torch.Tensor) -> torch.Tensor:
+        """The static-shape step at the decoder's positions: the token and the
+        positions go into their static tensors, then the graph's replay or the
+        step itself."""
+        if self._step is None:
+            self._graph_setup(tok)
+        self._tok.copy_(tok)
+        self._set_pos()
+        if self.graph:
+            self._g.replay()
+            out = self._out.clone()
+        else:
+            out = self._step()
+        if self.sampling:
+            self.last_logits = self._step_logits
+        return out
+
     def _decode_step_ragged(self, tok: torch.Tensor) -> torch.Tensor:
         for b in range(self.batch):
             if self.active[b] and self.pos_b[b] >= self.context:
@@ -974,17 +973,7 @@ class LlamaDecoder:
         if self.paged:
             self._grow_pages()  # before any launch; PoolExhausted leaves everything as it was
         if self.fp8:
-            if self._step is None:
-                self._graph_setup(tok)
-            self._tok.copy_(tok)
-            self._set_pos()
-            if self.graph:
-                self._g.replay()
-                out = self._out.clone()
-            else:
-                out = self._step()
-            if self.sampling:
-                self.last_logits = self._step_logits
+            out = self._static_step(tok)
         elif self.paged:
             logits = self._forward_paged(tok, list(self.pos_b), [int(a) for a in self.active])
             out = self._pick(logits, [p + 1 if a else -1 for p, a in zip(self.pos_b, self.active)])
@@ -1002,17 +991,7 @@ class LlamaDecoder:
         if self.pos >= self.context:
             self.pos = self.context // 2  # slide: keep the cache bounded for long runs
         if self.static:
-            if self._step is None:
-                self._graph_setup(tok)
-            self._tok.copy_(tok)
-            self._set_pos()
-            if self.graph:
-                self._g.replay()
-                out = self._out.clone()
-            else:
-                out = self._step()
-            if self.sampling:
-                self.last_logits = self._step_logits
+            out = self._static_step(tok)
             self.pos += 1
             return out
         if self.fp8:

@@ -7,6 +7,7 @@ falling back to eager PyTorch.
 from __future__ import annotations
 
 import ctypes as C
+import operator
 from typing import Optional
 
 import torch
@@ -76,125 +77,6 @@ def rope_dpos(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos_t: torc
     return y
 
 
-def _need_dpos(pos_t: torch.Tensor, what: str):
-    """The device-resident position of the graph-captured decode step: one int32
-    on the GPU.  Only the host side is checked; reading the value would force a
-    sync inside a captured graph."""
-    if not isinstance(pos_t, torch.Tensor) or pos_t.dtype != torch.int32 or pos_t.numel() != 1:
-        raise ValueError(f"{what}: pos_t must be a 1-element int32 tensor, got "
-                         f"{getattr(pos_t, 'dtype', type(pos_t))} {tuple(getattr(pos_t, 'shape', ()))}")
-    if not pos_t.is_cuda:
-        raise ValueError(f"{what}: pos_t must be a CUDA tensor (the kernel reads it), got {pos_t.device}")
-
-
-def qkv_rope_cache(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos_t: torch.Tensor, kc: torch.Tensor,
-                   vc: torch.Tensor, n_heads: int) -> torch.Tensor:
-    """One-token decode: split the packed qkv [B, 1, (H + 2 Hkv) hd], RoPE q and k
-    at the device position pos_t (int32 [1]), write k / v into the caches
-    [B, Hkv, C, hd] at that row, return q [B, H, hd].  No bounds check on the
-    device value: the caller keeps 0 <= pos < C."""
-    if kc.dim() != 4 or vc.shape != kc.shape:
-        raise ValueError(f"qkv_rope_cache: caches {tuple(kc.shape)} / {tuple(vc.shape)} must be [B, Hkv, C, hd] of "
-                         f"one shape")
-    B, Hkv, Cn, hd = kc.shape
-    _need_dpos(pos_t, "qkv_rope_cache")
-    _need(qkv, "qkv_rope_cache qkv")
-    _need(kc, "qkv_rope_cache kc")
-    _need(vc, "qkv_rope_cache vc")
-    if qkv.numel() != B * (n_heads + 2 * Hkv) * hd or vc.shape != kc.shape or cos.shape[-1] * 2 != hd:
-        raise ValueError(f"qkv_rope_cache: qkv {tuple(qkv.shape)} vs cache {tuple(kc.shape)}, H={n_heads}")
-    # the kernel indexes the RoPE tables and the cache rows with the device
-    # position: the tables must cover every cache row, dtypes as it assumes
-    if cos.shape[0] < Cn or sin.shape != cos.shape or cos.dtype != torch.float32 or sin.dtype != torch.float32 \
-            or kc.dtype != torch.bfloat16 or vc.dtype != torch.bfloat16 or qkv.dtype != torch.bfloat16:
-        raise ValueError(f"qkv_rope_cache: rope tables {tuple(cos.shape)} {cos.dtype} must cover {Cn} cache rows "
-                         f"(fp32), caches/qkv bf16")
-    q = torch.empty(B, n_heads, hd, dtype=torch.bfloat16, device=qkv.device)
-    _check(lib().gpbs_hip_qkv_rope_cache(_ptr(qkv), _ptr(cos), _ptr(sin), _ptr(pos_t), _ptr(q), _ptr(kc), _ptr(vc),
-                                         B, n_heads, Hkv, Cn, hd, _stream()), "qkv_rope_cache")
-    return q
-
-
-def decode_attn(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, pos_t: torch.Tensor,
-                nsplit: Optional[int] = None) -> torch.Tensor:
-    """Grouped-query attention of one new token per sequence over cache rows
-    0..pos (pos_t int32 [1] on device): q [B, H, 128] -> [B, H * 128].  The keys
-    are split over `nsplit` workgroups per (batch, KV head) (flash-decoding,
-    default: enough to give the chip >= 256 workgroups) and merged by a combine
-    kernel.  Everything the kernel takes as a raw pointer is checked on the host
-    tensors before the library is touched, except the device value of pos_t:
-    reading it would force a sync inside a captured graph, so the caller keeps
-    0 <= pos (the kernel clamps pos + 1 to C)."""
-    if q.dim() != 3 or kc.dim() != 4 or vc.shape != kc.shape:
-        raise ValueError(f"decode_attn: q {tuple(q.shape)} must be [B, H, 128], caches {tuple(kc.shape)} / "
-                         f"{tuple(vc.shape)} [B, Hkv, C, 128] of one shape")
-    B, Hkv, Cn, hd = kc.shape
-    H = q.shape[1]
-    if hd != 128 or B < 1 or Hkv < 1 or Cn < 1 or q.shape != (B, H, hd):
-        raise ValueError(f"decode_attn: q {tuple(q.shape)} must be [B, H, 128] for caches {tuple(kc.shape)} "
-                         f"[B, Hkv, C, 128]")
-    if H % Hkv or (H // Hkv) not in (1, 2, 4, 8):
-        raise ValueError(f"decode_attn: group size H / Hkv = {H} / {Hkv} must be 1, 2, 4 or 8")
-    for name, t in (("q", q), ("kc", kc), ("vc", vc)):
-        if t.dtype != torch.bfloat16:
-            raise ValueError(f"decode_attn: {name} must be bf16, got {t.dtype}")
-        if not t.is_contiguous():
-            raise ValueError(f"decode_attn: {name} must be contiguous (strides {t.stride()})")
-    if nsplit is not None and (not isinstance(nsplit, int) or isinstance(nsplit, bool) or nsplit < 1):
-        raise ValueError(f"decode_attn: nsplit={nsplit!r} must be None or an int >= 1")
-    _need_dpos(pos_t, "decode_attn")
-    _need(q, "decode_attn q")
-    _need(kc, "decode_attn kc")
-    _need(vc, "decode_attn vc")
-    out = torch.empty(B, H * hd, dtype=torch.bfloat16, device=q.device)
-    if nsplit is None:
-        nsplit = max(1, min(8, -(-256 // (B * Hkv)), -(-Cn // 64)))
-    ws = torch.empty(B * Hkv * nsplit * (H // Hkv) * (hd + 2), dtype=torch.float32, device=q.device) \
-        if nsplit > 1 else None
-    _check(lib().gpbs_hip_decode_attn(_ptr(q), _ptr(kc), _ptr(vc), _ptr(pos_t), _ptr(out), _ptr(ws), nsplit, B, H,
-                                      Hkv, Cn, hd, C.c_float(hd ** -0.5), _stream()), "decode_attn")
-    return out
-
-
-# --------------------------------------------------------------------------- prefill (csrc/hip/prefill_kernels.hip)
-def _prefill_geom(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, pos: int, what: str):
-    """Shape contract of k_prefill_attn, checked on the host tensors alone."""
-    if q.dim() != 4 or kc.dim() != 4 or vc.shape != kc.shape:
-        raise ValueError(f"{what}: q {tuple(q.shape)} must be [B, S, H, hd], caches {tuple(kc.shape)} / "
-                         f"{tuple(vc.shape)} [B, Hkv, C, hd]")
-    B, S, H, hd = q.shape
-    Bc, Hkv, Cn, hdc = kc.shape
-    if hd != 128 or hdc != 128:
-        raise ValueError(f"{what}: head_dim 128 required, got q {hd} / cache {hdc}")
-    if Bc != B or S < 1 or Hkv < 1 or H % Hkv or (H // Hkv) not in (1, 2, 4, 8):
-        raise ValueError(f"{what}: q {tuple(q.shape)} vs cache {tuple(kc.shape)} (same batch, group size "
-                         f"H / Hkv in 1/2/4/8)")
-    if not isinstance(pos, int) or isinstance(pos, bool) or pos < 0 or pos + S > Cn:
-        raise ValueError(f"{what}: pos={pos!r} with S={S} must satisfy 0 <= pos and pos + S <= C={Cn}")
-    for name, t in (("q", q), ("kc", kc), ("vc", vc)):
-        if t.dtype != torch.bfloat16:
-            raise ValueError(f"{what}: {name} must be bf16, got {t.dtype}")
-        if not t.is_contiguous():
-            raise ValueError(f"{what}: {name} must be contiguous (strides {t.stride()})")
-    return B, S, H, Hkv, Cn, hd
-
-
-def prefill_attn(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, pos: int) -> torch.Tensor:
-    """Causal grouped-query attention of S new tokens over the static KV cache
-    (k_prefill_attn, bf16 MFMA): q [B, S, H, 128] (RoPE applied), caches
-    [B, Hkv, C, 128] already holding rows pos .. pos + S - 1; query s attends
-    cache rows 0 .. pos + s.  Returns [B, S, H * 128] bf16.  Rows >= pos + S of
-    the caches are never read."""
-    B, S, H, Hkv, Cn, hd = _prefill_geom(q, kc, vc, pos, "prefill_attn")
-    _need(q, "prefill_attn q")
-    _need(kc, "prefill_attn kc")
-    _need(vc, "prefill_attn vc")
-    out = torch.empty(B, S, H * hd, dtype=torch.bfloat16, device=q.device)
-    _check(lib().gpbs_hip_prefill_attn(_ptr(q), _ptr(kc), _ptr(vc), _ptr(out), B, S, H, Hkv, Cn, hd, pos,
-                                       C.c_float(hd ** -0.5), _stream()), "prefill_attn")
-    return out
-
-
 def prefill_attn_ref(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, pos: int) -> torch.Tensor:
     """Plain-torch reference of prefill_attn for any head_dim / group size (runs
     on CPU too): fp32 compute, fp64 for fp64 inputs, grouped per KV head without
@@ -215,42 +97,6 @@ def prefill_attn_ref(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, pos: i
     return o.permute(0, 3, 1, 2, 4).reshape(B, S, H * hd)
 
 
-def qkv_rope_cache_prefill(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: int, kc: torch.Tensor,
-                           vc: torch.Tensor, n_heads: int) -> torch.Tensor:
-    """S-token form of qkv_rope_cache with a host position: split the packed qkv
-    [B, S, (H + 2 Hkv) hd], RoPE q and k at angle rows pos + s, write k / v into
-    rows pos .. pos + S - 1 of the caches [B, Hkv, C, hd]; returns q [B, S, H, hd]."""
-    if qkv.dim() != 3 or kc.dim() != 4 or vc.shape != kc.shape:
-        raise ValueError(f"qkv_rope_cache_prefill: qkv {tuple(qkv.shape)} must be [B, S, (H + 2 Hkv) hd], caches "
-                         f"{tuple(kc.shape)} / {tuple(vc.shape)}")
-    B, Hkv, Cn, hd = kc.shape
-    S = qkv.shape[1]
-    if qkv.shape[0] != B or S < 1 or qkv.shape[2] != (n_heads + 2 * Hkv) * hd or hd % 8 or cos.dim() != 2 \
-            or cos.shape[-1] * 2 != hd:
-        raise ValueError(f"qkv_rope_cache_prefill: qkv {tuple(qkv.shape)} vs cache {tuple(kc.shape)}, H={n_heads}, "
-                         f"rope tables {tuple(cos.shape)}")
-    if not isinstance(pos, int) or isinstance(pos, bool) or pos < 0 or pos + S > Cn:
-        raise ValueError(f"qkv_rope_cache_prefill: pos={pos!r} with S={S} must satisfy 0 <= pos and "
-                         f"pos + S <= C={Cn}")
-    if cos.shape[0] < pos + S or sin.shape != cos.shape or cos.dtype != torch.float32 or sin.dtype != torch.float32 \
-            or not (cos.is_contiguous() and sin.is_contiguous()):
-        raise ValueError(f"qkv_rope_cache_prefill: rope tables {tuple(cos.shape)} {cos.dtype} must be contiguous "
-                         f"fp32 and cover pos + S = {pos + S} rows")
-    for name, t in (("qkv", qkv), ("kc", kc), ("vc", vc)):
-        if t.dtype != torch.bfloat16 or not t.is_contiguous():
-            raise ValueError(f"qkv_rope_cache_prefill: {name} must be contiguous bf16, got {t.dtype} strides "
-                             f"{t.stride()}")
-    _need(qkv, "qkv_rope_cache_prefill qkv")
-    _need(kc, "qkv_rope_cache_prefill kc")
-    _need(vc, "qkv_rope_cache_prefill vc")
-    if not (cos.is_cuda and sin.is_cuda):
-        raise ValueError("qkv_rope_cache_prefill: rope tables must be CUDA tensors")
-    q = torch.empty(B, S, n_heads, hd, dtype=torch.bfloat16, device=qkv.device)
-    _check(lib().gpbs_hip_qkv_rope_cache_prefill(_ptr(qkv), _ptr(cos), _ptr(sin), _ptr(q), _ptr(kc), _ptr(vc), B, S,
-                                                 n_heads, Hkv, Cn, hd, pos, _stream()), "qkv_rope_cache_prefill")
-    return q
-
-
 # --------------------------------------------------------------------------- per-sequence positions (ragged batches)
 # Slot rules, applied by the kernels themselves on the device values:
 #   decode   sequence b is active iff 0 <= pos[b] < C; it writes row pos[b] and
@@ -260,143 +106,10 @@ def qkv_rope_cache_prefill(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tens
 #            len[b] <= 0.
 # An idle slot / a padding token writes nothing to the caches and gets zero q
 # and output rows.
-def _need_seq(what: str, B: int, **vectors: torch.Tensor):
-    """The per-sequence device vectors of the _seq kernels (pos_t, len_t): each a
-    contiguous int32 [B] on the GPU.  Only the host side is checked (as
-    _need_dpos): the kernels clamp the values themselves."""
-    for name, t in vectors.items():
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 1 or t.numel() != B:
-            raise ValueError(f"{what}: {name} must be an int32 tensor of exactly B={B} elements, got "
-                             f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
-        if not t.is_contiguous():
-            raise ValueError(f"{what}: {name} must be contiguous (strides {t.stride()})")
-    for name, t in vectors.items():
-        if not t.is_cuda:
-            raise ValueError(f"{what}: {name} must be a CUDA tensor (the kernel reads it), got {t.device}")
-
-
 def seq_tokens(pos: int, length: int, S: int, Cn: int) -> int:
     """n_b of the prefill slot rule (the host twin of the kernels' clamp)."""
     pos, length = int(pos), int(length)
     return 0 if pos < 0 or pos >= Cn or length <= 0 else min(length, S, Cn - pos)
-
-
-def qkv_rope_cache_seq(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos_t: torch.Tensor,
-                       kc: torch.Tensor, vc: torch.Tensor, n_heads: int) -> torch.Tensor:
-    """qkv_rope_cache with one device position per sequence (pos_t int32 [B]):
-    an active sequence gets the arithmetic of qkv_rope_cache at pos_t[b]; an
-    idle one writes nothing to its caches and its q row is zero."""
-    if kc.dim() != 4 or vc.shape != kc.shape:
-        raise ValueError(f"qkv_rope_cache_seq: caches {tuple(kc.shape)} / {tuple(vc.shape)} must be [B, Hkv, C, hd] "
-                         f"of one shape")
-    B, Hkv, Cn, hd = kc.shape
-    _need_seq("qkv_rope_cache_seq", B, pos_t=pos_t)
-    _need(qkv, "qkv_rope_cache_seq qkv")
-    _need(kc, "qkv_rope_cache_seq kc")
-    _need(vc, "qkv_rope_cache_seq vc")
-    if qkv.numel() != B * (n_heads + 2 * Hkv) * hd or hd % 8 or cos.dim() != 2 or cos.shape[-1] * 2 != hd:
-        raise ValueError(f"qkv_rope_cache_seq: qkv {tuple(qkv.shape)} vs cache {tuple(kc.shape)}, H={n_heads}")
-    if cos.shape[0] < Cn or sin.shape != cos.shape or cos.dtype != torch.float32 or sin.dtype != torch.float32 \
-            or not (cos.is_cuda and sin.is_cuda and cos.is_contiguous() and sin.is_contiguous()):
-        raise ValueError(f"qkv_rope_cache_seq: rope tables {tuple(cos.shape)} {cos.dtype} must be contiguous fp32 "
-                         f"CUDA tensors covering {Cn} cache rows")
-    q = torch.empty(B, n_heads, hd, dtype=torch.bfloat16, device=qkv.device)
-    _check(lib().gpbs_hip_qkv_rope_cache_seq(_ptr(qkv), _ptr(cos), _ptr(sin), _ptr(pos_t), _ptr(q), _ptr(kc),
-                                             _ptr(vc), B, n_heads, Hkv, Cn, hd, _stream()), "qkv_rope_cache_seq")
-    return q
-
-
-def decode_attn_seq(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, pos_t: torch.Tensor,
-                    nsplit: Optional[int] = None) -> torch.Tensor:
-    """decode_attn with one device position per sequence (pos_t int32 [B]):
-    row b is bit-identical to decode_attn at pos = pos_t[b] with the same
-    nsplit; an idle sequence loads no cache row and its row is zero."""
-    if q.dim() != 3 or kc.dim() != 4 or vc.shape != kc.shape:
-        raise ValueError(f"decode_attn_seq: q {tuple(q.shape)} must be [B, H, 128], caches {tuple(kc.shape)} / "
-                         f"{tuple(vc.shape)} [B, Hkv, C, 128] of one shape")
-    B, Hkv, Cn, hd = kc.shape
-    H = q.shape[1]
-    if hd != 128 or B < 1 or Hkv < 1 or Cn < 1 or q.shape != (B, H, hd):
-        raise ValueError(f"decode_attn_seq: q {tuple(q.shape)} must be [B, H, 128] for caches {tuple(kc.shape)} "
-                         f"[B, Hkv, C, 128]")
-    if H % Hkv or (H // Hkv) not in (1, 2, 4, 8):
-        raise ValueError(f"decode_attn_seq: group size H / Hkv = {H} / {Hkv} must be 1, 2, 4 or 8")
-    for name, t in (("q", q), ("kc", kc), ("vc", vc)):
-        if t.dtype != torch.bfloat16:
-            raise ValueError(f"decode_attn_seq: {name} must be bf16, got {t.dtype}")
-        if not t.is_contiguous():
-            raise ValueError(f"decode_attn_seq: {name} must be contiguous (strides {t.stride()})")
-    if nsplit is not None and (not isinstance(nsplit, int) or isinstance(nsplit, bool) or nsplit < 1):
-        raise ValueError(f"decode_attn_seq: nsplit={nsplit!r} must be None or an int >= 1")
-    _need_seq("decode_attn_seq", B, pos_t=pos_t)
-    _need(q, "decode_attn_seq q")
-    _need(kc, "decode_attn_seq kc")
-    _need(vc, "decode_attn_seq vc")
-    out = torch.empty(B, H * hd, dtype=torch.bfloat16, device=q.device)
-    if nsplit is None:  # as decode_attn: from the shapes alone, so a row's split does not depend on its position
-        nsplit = max(1, min(8, -(-256 // (B * Hkv)), -(-Cn // 64)))
-    ws = torch.empty(B * Hkv * nsplit * (H // Hkv) * (hd + 2), dtype=torch.float32, device=q.device) \
-        if nsplit > 1 else None
-    _check(lib().gpbs_hip_decode_attn_seq(_ptr(q), _ptr(kc), _ptr(vc), _ptr(pos_t), _ptr(out), _ptr(ws), nsplit, B,
-                                          H, Hkv, Cn, hd, C.c_float(hd ** -0.5), _stream()), "decode_attn_seq")
-    return out
-
-
-def qkv_rope_cache_prefill_seq(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos_t: torch.Tensor,
-                               len_t: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor,
-                               n_heads: int) -> torch.Tensor:
-    """qkv_rope_cache_prefill with a device position and length per sequence
-    (int32 [B] each): token s < n_b of sequence b is rotated at angle row
-    pos_t[b] + s and written to that cache row; tokens s >= n_b write nothing
-    and their q rows are zero.  Returns q [B, S, H, hd]."""
-    what = "qkv_rope_cache_prefill_seq"
-    if qkv.dim() != 3 or kc.dim() != 4 or vc.shape != kc.shape:
-        raise ValueError(f"{what}: qkv {tuple(qkv.shape)} must be [B, S, (H + 2 Hkv) hd], caches "
-                         f"{tuple(kc.shape)} / {tuple(vc.shape)}")
-    B, Hkv, Cn, hd = kc.shape
-    S = qkv.shape[1]
-    if qkv.shape[0] != B or S < 1 or qkv.shape[2] != (n_heads + 2 * Hkv) * hd or hd % 8 or cos.dim() != 2 \
-            or cos.shape[-1] * 2 != hd:
-        raise ValueError(f"{what}: qkv {tuple(qkv.shape)} vs cache {tuple(kc.shape)}, H={n_heads}, "
-                         f"rope tables {tuple(cos.shape)}")
-    _need_seq(what, B, pos_t=pos_t, len_t=len_t)
-    # any row below C can be a sequence's position: the tables cover them all
-    if cos.shape[0] < Cn or sin.shape != cos.shape or cos.dtype != torch.float32 or sin.dtype != torch.float32 \
-            or not (cos.is_contiguous() and sin.is_contiguous()):
-        raise ValueError(f"{what}: rope tables {tuple(cos.shape)} {cos.dtype} must be contiguous fp32 and cover "
-                         f"C = {Cn} rows")
-    for name, t in (("qkv", qkv), ("kc", kc), ("vc", vc)):
-        if t.dtype != torch.bfloat16 or not t.is_contiguous():
-            raise ValueError(f"{what}: {name} must be contiguous bf16, got {t.dtype} strides {t.stride()}")
-    _need(qkv, f"{what} qkv")
-    _need(kc, f"{what} kc")
-    _need(vc, f"{what} vc")
-    if not (cos.is_cuda and sin.is_cuda):
-        raise ValueError(f"{what}: rope tables must be CUDA tensors")
-    q = torch.empty(B, S, n_heads, hd, dtype=torch.bfloat16, device=qkv.device)
-    _check(lib().gpbs_hip_qkv_rope_cache_prefill_seq(_ptr(qkv), _ptr(cos), _ptr(sin), _ptr(pos_t), _ptr(len_t),
-                                                     _ptr(q), _ptr(kc), _ptr(vc), B, S, n_heads, Hkv, Cn, hd,
-                                                     _stream()), what)
-    return q
-
-
-def prefill_attn_seq(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, pos_t: torch.Tensor,
-                     len_t: torch.Tensor) -> torch.Tensor:
-    """prefill_attn with a device position and length per sequence (int32 [B]
-    each): q [B, S, H, 128] padded to the longest sequence; query s < n_b of
-    sequence b attends cache rows 0 .. pos_t[b] + s and its row is bit-identical
-    to prefill_attn on that sequence alone with (S = n_b, pos = pos_t[b]).  Rows
-    s >= n_b of the result are zero, their q rows are never loaded, and no cache
-    row past pos_t[b] + n_b - 1 is addressed.  Returns [B, S, H * 128] bf16."""
-    B, S, H, Hkv, Cn, hd = _prefill_geom(q, kc, vc, 0, "prefill_attn_seq")
-    _need_seq("prefill_attn_seq", B, pos_t=pos_t, len_t=len_t)
-    _need(q, "prefill_attn_seq q")
-    _need(kc, "prefill_attn_seq kc")
-    _need(vc, "prefill_attn_seq vc")
-    out = torch.zeros(B, S, H * hd, dtype=torch.bfloat16, device=q.device)  # the kernel stores rows < n_b only
-    _check(lib().gpbs_hip_prefill_attn_seq(_ptr(q), _ptr(kc), _ptr(vc), _ptr(pos_t), _ptr(len_t), _ptr(out), B, S, H,
-                                           Hkv, Cn, hd, C.c_float(hd ** -0.5), _stream()), "prefill_attn_seq")
-    return out
 
 
 def attn_seq_ref(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, pos, lens) -> torch.Tensor:
@@ -430,140 +143,6 @@ def attn_seq_ref(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, pos, lens)
 # read entry outside [0, P) forms no address outside the pools: the write
 # through it is dropped, the reads through it come from page 0.
 PAGE_SIZES = (64, 128, 256)
-
-
-def _need_paged(what: str, kpool: torch.Tensor, vpool: torch.Tensor, table: torch.Tensor, B: Optional[int] = None):
-    """Host-side checks of the pools and the block table; returns
-    (B, NP, P, Hkv, page, hd).  The table's values are not read (as _need_seq)."""
-    if not isinstance(kpool, torch.Tensor) or not isinstance(vpool, torch.Tensor) or kpool.dim() != 4 \
-            or vpool.shape != kpool.shape:
-        raise ValueError(f"{what}: pools {tuple(getattr(kpool, 'shape', ()))} / {tuple(getattr(vpool, 'shape', ()))} "
-                         f"must be [P, Hkv, page, 128] of one shape")
-    P, Hkv, page, hd = kpool.shape
-    if page not in PAGE_SIZES or hd != 128 or P < 1 or Hkv < 1:
-        raise ValueError(f"{what}: pools {tuple(kpool.shape)} must be [P, Hkv, page, 128] with page in {PAGE_SIZES}")
-    for name, t in (("kpool", kpool), ("vpool", vpool)):
-        if t.dtype != torch.bfloat16 or not t.is_contiguous():
-            raise ValueError(f"{what}: {name} must be contiguous bf16, got {t.dtype} strides {t.stride()}")
-    if not isinstance(table, torch.Tensor) or table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] < 1 \
-            or (B is not None and table.shape[0] != B):
-        raise ValueError(f"{what}: table must be an int32 tensor [B{'' if B is None else '=' + str(B)}, NP >= 1], got "
-                         f"{getattr(table, 'dtype', type(table))} {tuple(getattr(table, 'shape', ()))}")
-    if not table.is_contiguous():
-        raise ValueError(f"{what}: table must be contiguous (strides {table.stride()})")
-    if not table.is_cuda:
-        raise ValueError(f"{what}: table must be a CUDA tensor (the kernel reads it), got {table.device}")
-    _need(kpool, f"{what} kpool")
-    _need(vpool, f"{what} vpool")
-    return table.shape[0], table.shape[1], P, Hkv, page, hd
-
-
-def qkv_rope_cache_paged(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos_t: torch.Tensor,
-                         table: torch.Tensor, kpool: torch.Tensor, vpool: torch.Tensor, n_heads: int) -> torch.Tensor:
-    """qkv_rope_cache_seq through a block table: an active sequence
-    (0 <= pos_t[b] < NP * page) gets the same q and writes the same k / v row,
-    into row pos_t[b] % page of page table[b, pos_t[b] // page]."""
-    what = "qkv_rope_cache_paged"
-    B, NP, P, Hkv, page, hd = _need_paged(what, kpool, vpool, table)
-    Cl = NP * page
-    _need_seq(what, B, pos_t=pos_t)
-    _need(qkv, f"{what} qkv")
-    if qkv.numel() != B * (n_heads + 2 * Hkv) * hd or cos.dim() != 2 or cos.shape[-1] * 2 != hd:
-        raise ValueError(f"{what}: qkv {tuple(qkv.shape)} vs pools {tuple(kpool.shape)}, B={B}, H={n_heads}")
-    if cos.shape[0] < Cl or sin.shape != cos.shape or cos.dtype != torch.float32 or sin.dtype != torch.float32 \
-            or not (cos.is_cuda and sin.is_cuda and cos.is_contiguous() and sin.is_contiguous()):
-        raise ValueError(f"{what}: rope tables {tuple(cos.shape)} {cos.dtype} must be contiguous fp32 CUDA tensors "
-                         f"covering NP * page = {Cl} rows")
-    q = torch.empty(B, n_heads, hd, dtype=torch.bfloat16, device=qkv.device)
-    _check(lib().gpbs_hip_qkv_rope_cache_paged(_ptr(qkv), _ptr(cos), _ptr(sin), _ptr(pos_t), _ptr(table), _ptr(q),
-                                               _ptr(kpool), _ptr(vpool), B, n_heads, Hkv, NP, P, page, hd, _stream()),
-           what)
-    return q
-
-
-def decode_attn_paged(q: torch.Tensor, kpool: torch.Tensor, vpool: torch.Tensor, table: torch.Tensor,
-                      pos_t: torch.Tensor, nsplit: Optional[int] = None) -> torch.Tensor:
-    """decode_attn_seq through a block table: row b is bit-identical to
-    decode_attn_seq on the dense cache of Cl = NP * page rows gathered from
-    sequence b's pages, with the same nsplit (default: from (B, Hkv, Cl))."""
-    what = "decode_attn_paged"
-    B, NP, P, Hkv, page, hd = _need_paged(what, kpool, vpool, table)
-    Cl = NP * page
-    if q.dim() != 3 or q.shape[0] != B or q.shape[2] != hd:
-        raise ValueError(f"{what}: q {tuple(q.shape)} must be [B={B}, H, 128]")
-    H = q.shape[1]
-    if H % Hkv or (H // Hkv) not in (1, 2, 4, 8):
-        raise ValueError(f"{what}: group size H / Hkv = {H} / {Hkv} must be 1, 2, 4 or 8")
-    if q.dtype != torch.bfloat16 or not q.is_contiguous():
-        raise ValueError(f"{what}: q must be contiguous bf16, got {q.dtype} strides {q.stride()}")
-    if nsplit is not None and (not isinstance(nsplit, int) or isinstance(nsplit, bool) or nsplit < 1):
-        raise ValueError(f"{what}: nsplit={nsplit!r} must be None or an int >= 1")
-    _need_seq(what, B, pos_t=pos_t)
-    _need(q, f"{what} q")
-    out = torch.empty(B, H * hd, dtype=torch.bfloat16, device=q.device)
-    if nsplit is None:  # as decode_attn_seq, with Cl for C
-        nsplit = max(1, min(8, -(-256 // (B * Hkv)), -(-Cl // 64)))
-    ws = torch.empty(B * Hkv * nsplit * (H // Hkv) * (hd + 2), dtype=torch.float32, device=q.device) \
-        if nsplit > 1 else None
-    _check(lib().gpbs_hip_decode_attn_paged(_ptr(q), _ptr(kpool), _ptr(vpool), _ptr(pos_t), _ptr(table), _ptr(out),
-                                            _ptr(ws), nsplit, B, H, Hkv, NP, P, page, hd, C.c_float(hd ** -0.5),
-                                            _stream()), what)
-    return out
-
-
-def qkv_rope_cache_prefill_paged(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos_t: torch.Tensor,
-                                 len_t: torch.Tensor, table: torch.Tensor, kpool: torch.Tensor, vpool: torch.Tensor,
-                                 n_heads: int) -> torch.Tensor:
-    """qkv_rope_cache_prefill_seq through a block table: token s < n_b of
-    sequence b (n_b from Cl = NP * page) is written to logical row pos_t[b] + s
-    of its pages.  Returns q [B, S, H, hd]."""
-    what = "qkv_rope_cache_prefill_paged"
-    B, NP, P, Hkv, page, hd = _need_paged(what, kpool, vpool, table)
-    Cl = NP * page
-    if qkv.dim() != 3 or qkv.shape[0] != B or qkv.shape[1] < 1 or qkv.shape[2] != (n_heads + 2 * Hkv) * hd \
-            or cos.dim() != 2 or cos.shape[-1] * 2 != hd:
-        raise ValueError(f"{what}: qkv {tuple(qkv.shape)} must be [B={B}, S, (H + 2 Hkv) hd] for pools "
-                         f"{tuple(kpool.shape)}, H={n_heads}, rope tables {tuple(cos.shape)}")
-    S = qkv.shape[1]
-    _need_seq(what, B, pos_t=pos_t, len_t=len_t)
-    if cos.shape[0] < Cl or sin.shape != cos.shape or cos.dtype != torch.float32 or sin.dtype != torch.float32 \
-            or not (cos.is_contiguous() and sin.is_contiguous()):
-        raise ValueError(f"{what}: rope tables {tuple(cos.shape)} {cos.dtype} must be contiguous fp32 and cover "
-                         f"NP * page = {Cl} rows")
-    if qkv.dtype != torch.bfloat16 or not qkv.is_contiguous():
-        raise ValueError(f"{what}: qkv must be contiguous bf16, got {qkv.dtype} strides {qkv.stride()}")
-    _need(qkv, f"{what} qkv")
-    if not (cos.is_cuda and sin.is_cuda):
-        raise ValueError(f"{what}: rope tables must be CUDA tensors")
-    q = torch.empty(B, S, n_heads, hd, dtype=torch.bfloat16, device=qkv.device)
-    _check(lib().gpbs_hip_qkv_rope_cache_prefill_paged(_ptr(qkv), _ptr(cos), _ptr(sin), _ptr(pos_t), _ptr(len_t),
-                                                       _ptr(table), _ptr(q), _ptr(kpool), _ptr(vpool), B, S, n_heads,
-                                                       Hkv, NP, P, page, hd, _stream()), what)
-    return q
-
-
-def prefill_attn_paged(q: torch.Tensor, kpool: torch.Tensor, vpool: torch.Tensor, table: torch.Tensor,
-                       pos_t: torch.Tensor, len_t: torch.Tensor) -> torch.Tensor:
-    """prefill_attn_seq through a block table: rows s < n_b of sequence b are
-    bit-identical to prefill_attn_seq on the dense cache gathered from its
-    pages; no row past pos_t[b] + n_b - 1 is addressed, through any page.
-    Returns [B, S, H * 128] bf16, rows s >= n_b zero."""
-    what = "prefill_attn_paged"
-    B, NP, P, Hkv, page, hd = _need_paged(what, kpool, vpool, table)
-    if q.dim() != 4 or q.shape[0] != B or q.shape[1] < 1 or q.shape[3] != hd:
-        raise ValueError(f"{what}: q {tuple(q.shape)} must be [B={B}, S, H, 128]")
-    S, H = q.shape[1], q.shape[2]
-    if H % Hkv or (H // Hkv) not in (1, 2, 4, 8):
-        raise ValueError(f"{what}: group size H / Hkv = {H} / {Hkv} must be 1, 2, 4 or 8")
-    if q.dtype != torch.bfloat16 or not q.is_contiguous():
-        raise ValueError(f"{what}: q must be contiguous bf16, got {q.dtype} strides {q.stride()}")
-    _need_seq(what, B, pos_t=pos_t, len_t=len_t)
-    _need(q, f"{what} q")
-    out = torch.zeros(B, S, H * hd, dtype=torch.bfloat16, device=q.device)  # the kernel stores rows < n_b only
-    _check(lib().gpbs_hip_prefill_attn_paged(_ptr(q), _ptr(kpool), _ptr(vpool), _ptr(pos_t), _ptr(len_t), _ptr(table),
-                                             _ptr(out), B, S, H, Hkv, NP, P, page, hd, C.c_float(hd ** -0.5),
-                                             _stream()), what)
-    return out
 
 
 def paged_gather(pool: torch.Tensor, table_row, rows: int) -> torch.Tensor:
@@ -665,34 +244,422 @@ def kv8_emulate_rows(kpool: torch.Tensor, vpool: torch.Tensor, table: torch.Tens
         pool[pgv, :, prv] = kv8_round(pool[pgv, :, prv])  # [rows, Hkv, hd]
 
 
-def _need_paged_kv8(what: str, kpool8: torch.Tensor, vpool8: torch.Tensor, kscale: torch.Tensor,
-                    vscale: torch.Tensor, table: torch.Tensor):
-    """Host-side checks of the four cache tensors and the block table; returns
-    (B, NP, P, Hkv, page, hd).  As _need_paged, for the fp8 pools."""
-    if not isinstance(kpool8, torch.Tensor) or not isinstance(vpool8, torch.Tensor) or kpool8.dim() != 4 \
-            or vpool8.shape != kpool8.shape:
-        raise ValueError(f"{what}: pools {tuple(getattr(kpool8, 'shape', ()))} / "
-                         f"{tuple(getattr(vpool8, 'shape', ()))} must be [P, Hkv, page, 128] of one shape")
-    P, Hkv, page, hd = kpool8.shape
-    if page not in PAGE_SIZES or hd != 128 or P < 1 or Hkv < 1:
-        raise ValueError(f"{what}: pools {tuple(kpool8.shape)} must be [P, Hkv, page, 128] with page in {PAGE_SIZES}")
-    for name, t in (("kpool8", kpool8), ("vpool8", vpool8)):
-        if t.dtype != torch.float8_e4m3fn or not t.is_contiguous():
-            raise ValueError(f"{what}: {name} must be contiguous float8_e4m3fn, got {t.dtype} strides {t.stride()}")
-    for name, t in (("kscale", kscale), ("vscale", vscale)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (P, Hkv, page) \
-                or not t.is_contiguous():
-            raise ValueError(f"{what}: {name} must be a contiguous fp32 tensor [P, Hkv, page] = {(P, Hkv, page)}, got "
+def attn_paged_kv8_ref(q: torch.Tensor, kpool8: torch.Tensor, vpool8: torch.Tensor, kscale: torch.Tensor,
+                       vscale: torch.Tensor, table, pos, lens) -> torch.Tensor:
+    """Plain-torch reference of the two _kv8 attention kernels: attn_paged_ref
+    over the dequantised pools."""
+    return attn_paged_ref(q, kv8_dequant(kpool8, kscale), kv8_dequant(vpool8, vscale), table, pos, lens)
+
+
+# --------------------------------------------------------------------------- cache views (csrc/hip/attn_cache.hpp)
+# The attention block of a layer is two launches: "write" splits the packed qkv, applies RoPE to q and k and stores
+# k / v into the cache; "attend" runs grouped-query attention of the new tokens over it.  Each exists for one new
+# token per sequence (decode_kernels.hip) and for S of them (prefill_kernels.hip), and in the four cache forms of
+# attn_cache.hpp.  The classes below are the host side of those forms.  A view holds the cache tensors of one layer
+# (`cache`, in the order of the C ABI, named `names` in messages) and what addresses them, and answers only what the
+# forms differ in:
+#   entry                   (name in messages, library symbol) of its four entry points, indexed by WRITE_DECODE ..
+#   check(what, S, attend)  its host-side checks (type, dtype, rank, sizes, strides; no device, no device value) for
+#                           a decode launch (S None) or a prefill launch of S new tokens, `attend` for the attention
+#                           launch; returns (B, Hkv, hd, rows) with rows = C or NP * page per sequence
+#   args(S)                 its part of an entry point's arguments: the names and the device tensors that address the
+#                           cache, the geometry before hd, the host position after it
+#   wrote(S)                if not None, runs after the write launch
+# Everything else (q / qkv, the RoPE tables, nsplit, the workspace, the result, the call) is in write_decode /
+# attend_decode / write_prefill / attend_prefill, once for all forms.  Pointers go to the library as plain ints
+# (data_ptr()), which its c_void_p prototypes take.
+WRITE_DECODE, ATTEND_DECODE, WRITE_PREFILL, ATTEND_PREFILL = range(4)
+
+
+def _entry(suffix: str):
+    return tuple((op + suffix, "gpbs_hip_" + op + suffix)
+                 for op in ("qkv_rope_cache", "decode_attn", "qkv_rope_cache_prefill", "prefill_attn"))
+
+
+def _need_vectors(what: str, B: int, vectors):
+    """The per-sequence device vectors (pos_t, len_t): each a contiguous int32 [B].  Only the host side is checked:
+    the kernels clamp the values themselves, and reading one would force a sync inside a captured graph."""
+    for name, t in vectors:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.dim() != 1 or t.numel() != B:
+            raise ValueError(f"{what}: {name} must be an int32 tensor of exactly B={B} elements, got "
                              f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
-    if not isinstance(table, torch.Tensor) or table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] < 1:
-        raise ValueError(f"{what}: table must be an int32 tensor [B, NP >= 1], got "
-                         f"{getattr(table, 'dtype', type(table))} {tuple(getattr(table, 'shape', ()))}")
-    if not table.is_contiguous():
-        raise ValueError(f"{what}: table must be contiguous (strides {table.stride()})")
-    for name, t in (("table", table), ("kpool8", kpool8), ("vpool8", vpool8), ("kscale", kscale), ("vscale", vscale)):
-        if not t.is_cuda:
-            raise ValueError(f"{what}: {name} must be a CUDA tensor (the kernel reads it), got {t.device}")
-    return table.shape[0], table.shape[1], P, Hkv, page, hd
+        if not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be contiguous (strides {t.stride()})")
+
+
+_BF16, _F32 = torch.bfloat16, torch.float32
+
+
+def _need_layout(what: str, dtype, dtype_name: str, names, a, b):
+    """Two tensors of one dtype, both contiguous."""
+    if a.dtype is not dtype or b.dtype is not dtype or not (a.is_contiguous() and b.is_contiguous()):
+        for name, t in zip(names, (a, b)):
+            if t.dtype is not dtype:
+                raise ValueError(f"{what}: {name} must be {dtype_name}, got {t.dtype}")
+            if not t.is_contiguous():
+                raise ValueError(f"{what}: {name} must be contiguous (strides {t.stride()})")
+
+
+def _need_dense(what: str, kc, vc):
+    """The dense caches of DenseUniform / DenseSeq; returns (B, Hkv, C, hd)."""
+    shape = kc.shape  # read once: every .shape builds a new torch.Size
+    if len(shape) != 4 or vc.shape != shape:
+        raise ValueError(f"{what}: caches {tuple(shape)} / {tuple(vc.shape)} must be [B, Hkv, C, hd] of one shape")
+    B, Hkv, Cn, hd = shape
+    if B < 1 or Hkv < 1 or Cn < 1 or hd < 8 or hd % 8:
+        raise ValueError(f"{what}: caches {tuple(shape)} must be [B, Hkv, C, hd], none empty, hd % 8 == 0")
+    _need_layout(what, _BF16, "bf16", ("kc", "vc"), kc, vc)
+    return B, Hkv, Cn, hd
+
+
+class DenseUniform:
+    """Caches kc / vc bf16 [B, Hkv, C, hd], every sequence at the position `pos`: an int32 [1] device tensor for the
+    decode launches (the kernel reads it at run time: valid inside a captured graph; the caller keeps 0 <= pos < C),
+    a host int for the prefill ones, whose S tokens go to rows pos .. pos + S - 1."""
+    entry, names = _entry(""), ("kc", "vc")
+    partial = False  # attend_prefill stores every row of its result
+    wrote = None
+
+    def __init__(self, kc, vc, pos):
+        self.cache, self.pos = (kc, vc), pos
+
+    def check(self, what: str, S, attend: bool):
+        B, Hkv, Cn, hd = _need_dense(what, *self.cache)
+        pos = self.pos
+        if S is None:
+            if not isinstance(pos, torch.Tensor) or pos.dtype != torch.int32 or pos.numel() != 1:
+                raise ValueError(f"{what}: pos_t must be a 1-element int32 tensor, got "
+                                 f"{getattr(pos, 'dtype', type(pos))} {tuple(getattr(pos, 'shape', ()))}")
+        elif not isinstance(pos, int) or isinstance(pos, bool) or pos < 0 or pos + S > Cn:
+            raise ValueError(f"{what}: pos={pos!r} with S={S} must satisfy 0 <= pos and pos + S <= C={Cn}")
+        return B, Hkv, hd, Cn
+
+    def args(self, S):
+        Cn = self.cache[0].shape[2]
+        return (("pos_t",), (self.pos,), (Cn,), ()) if S is None else ((), (), (Cn,), (self.pos,))
+
+
+class DenseSeq:
+    """The same caches with one device position per sequence, pos_t int32 [B], and for prefill one length, len_t
+    int32 [B], under the slot rules above."""
+    entry, names = _entry("_seq"), ("kc", "vc")
+    partial = True  # attend_prefill stores rows s < n_b only: its result starts as zeros
+    wrote = None
+
+    def __init__(self, kc, vc, pos_t, len_t=None):
+        self.cache, self.pos_t, self.len_t = (kc, vc), pos_t, len_t
+
+    def check(self, what: str, S, attend: bool):
+        B, Hkv, Cn, hd = _need_dense(what, *self.cache)
+        if S is None:
+            _need_vectors(what, B, (("pos_t", self.pos_t),))
+        else:
+            if attend and S > Cn:  # the attention launch is sized for S
+                raise ValueError(f"{what}: S={S} must satisfy pos + S <= C={Cn} at pos = 0")
+            _need_vectors(what, B, (("pos_t", self.pos_t), ("len_t", self.len_t)))
+        return B, Hkv, hd, Cn
+
+    def args(self, S):
+        Cn = self.cache[0].shape[2]
+        if S is None:
+            return ("pos_t",), (self.pos_t,), (Cn,), ()
+        return ("pos_t", "len_t"), (self.pos_t, self.len_t), (Cn,), ()
+
+
+class Paged:
+    """Pools kpool / vpool bf16 [P, Hkv, page, 128] behind the block table `table` int32 [B, NP], with pos_t / len_t
+    as DenseSeq and NP * page rows per sequence (the paged rules above)."""
+    entry, names, dtype, dtype_name = _entry("_paged"), ("kpool", "vpool"), torch.bfloat16, "bf16"
+    partial = True
+    wrote = None
+
+    def __init__(self, kpool, vpool, table, pos_t, len_t=None):
+        self.cache, self.scales = (kpool, vpool), ()
+        self.table, self.pos_t, self.len_t = table, pos_t, len_t
+
+    def check(self, what: str, S, attend: bool):
+        """One check for both pool dtypes: `scales` is empty here and (kscale, vscale) in PagedKv8."""
+        kp, vp, table = self.cache[0], self.cache[1], self.table
+        if not isinstance(kp, torch.Tensor) or not isinstance(vp, torch.Tensor) or kp.dim() != 4 \
+                or vp.shape != kp.shape:
+            raise ValueError(f"{what}: pools {tuple(getattr(kp, 'shape', ()))} / {tuple(getattr(vp, 'shape', ()))} "
+                             f"must be [P, Hkv, page, 128] of one shape")
+        P, Hkv, page, hd = kp.shape
+        if page not in PAGE_SIZES or hd != 128 or P < 1 or Hkv < 1:
+            raise ValueError(f"{what}: pools {tuple(kp.shape)} must be [P, Hkv, page, 128] with page in {PAGE_SIZES}")
+        _need_layout(what, self.dtype, self.dtype_name, self.names, kp, vp)
+        for name, t in zip(("kscale", "vscale"), self.scales):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (P, Hkv, page) \
+                    or not t.is_contiguous():
+                raise ValueError(f"{what}: {name} must be a contiguous fp32 tensor [P, Hkv, page] = {(P, Hkv, page)}, "
+                                 f"got {getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+        if not isinstance(table, torch.Tensor) or table.dtype != torch.int32 or table.dim() != 2 \
+                or table.shape[0] < 1 or table.shape[1] < 1:
+            raise ValueError(f"{what}: table must be an int32 tensor [B >= 1, NP >= 1], got "
+                             f"{getattr(table, 'dtype', type(table))} {tuple(getattr(table, 'shape', ()))}")
+        if not table.is_contiguous():
+            raise ValueError(f"{what}: table must be contiguous (strides {table.stride()})")
+        B, NP = table.shape
+        _need_vectors(what, B, (("pos_t", self.pos_t),) if S is None else
+                      (("pos_t", self.pos_t), ("len_t", self.len_t)))
+        return B, Hkv, hd, NP * page
+
+    def args(self, S):
+        P, _, page, _ = self.cache[0].shape
+        geom = (self.table.shape[1], P, page)
+        if S is None:
+            return ("pos_t", "table"), (self.pos_t, self.table), geom, ()
+        return ("pos_t", "len_t", "table"), (self.pos_t, self.len_t, self.table), geom, ()
+
+
+class PagedKv8(Paged):
+    """The fp8 paged cache: code pools kpool8 / vpool8 float8_e4m3fn [P, Hkv, page, 128] and the scales kscale /
+    vscale fp32 [P, Hkv, page] of the codec above."""
+    entry, names = _entry("_paged_kv8"), ("kpool8", "vpool8", "kscale", "vscale")
+    dtype, dtype_name = torch.float8_e4m3fn, "float8_e4m3fn"
+
+    def __init__(self, kpool8, vpool8, kscale, vscale, table, pos_t, len_t=None):
+        self.cache, self.scales = (kpool8, vpool8, kscale, vscale), (kscale, vscale)
+        self.table, self.pos_t, self.len_t = table, pos_t, len_t
+
+
+class PagedEmulated(Paged):
+    """The fp8 cache emulated on bf16 pools with the bf16 paged kernels: after the write launch, torch ops round
+    exactly the rows it stored through the codec (kv8_emulate_rows), so the attention launch reads what PagedKv8
+    would hold.  The oracle of PagedKv8; torch indexing between the launches, so not for a captured graph."""
+
+    def wrote(self, S):
+        kv8_emulate_rows(*self.cache, self.table, self.pos_t, None if S is None else self.len_t, S or 1)
+
+
+_DATA_PTR, _IS_CUDA = torch.Tensor.data_ptr, operator.attrgetter("is_cuda")
+
+
+def _need_cuda(what: str, tensors, *names):
+    """Every tensor an entry point reads or writes is on the GPU: asked last, of the addressing tensors first.
+    `names`: tuples of the tensors' names, put together only to name the first that is not."""
+    if not all(map(_IS_CUDA, tensors)):
+        name, t = next((name, t) for name, t in zip(sum(names, ()), tensors) if not t.is_cuda)
+        raise ValueError(f"{what}: {name} must be a CUDA tensor (the kernel reads it), got {t.device}")
+
+
+def _write(what: str, sym: str, view, qkv, cos, sin, S, rows, dims, hd):
+    """The part of write_decode / write_prefill after the shape of qkv: dims = (B, [S,] H, Hkv)."""
+    if qkv.dtype is not _BF16:
+        raise ValueError(f"{what}: qkv must be bf16, got {qkv.dtype}")
+    if not qkv.is_contiguous():
+        raise ValueError(f"{what}: qkv must be contiguous (strides {qkv.stride()})")
+    tables = cos.shape
+    if len(tables) != 2 or tables[1] * 2 != hd or sin.shape != tables:
+        raise ValueError(f"{what}: rope tables {tuple(tables)} / {tuple(sin.shape)} must be [rows, hd / 2] of one "
+                         f"shape for hd={hd}")
+    if cos.dtype is not _F32 or sin.dtype is not _F32 or not (cos.is_contiguous() and sin.is_contiguous()):
+        raise ValueError(f"{what}: rope tables {tuple(tables)} {cos.dtype} / {sin.dtype} must be contiguous fp32")
+    names, index, geom, tail = view.args(S)
+    need = tail[0] + S if tail else rows  # a host position: rows pos .. pos + S - 1; else any row can be a position
+    if tables[0] < need:
+        raise ValueError(f"{what}: rope tables {tuple(tables)} must cover {need} rows")
+    _need_cuda(what, (*index, qkv, cos, sin, *view.cache), names, ("qkv", "cos", "sin"), view.names)
+    q = torch.empty(*dims[:-1], hd, dtype=torch.bfloat16, device=qkv.device)
+    _check(getattr(lib(), sym)(*map(_DATA_PTR, (qkv, cos, sin, *index, q, *view.cache)), *dims, *geom, hd, *tail,
+                               _stream()), what)
+    if view.wrote is not None:
+        view.wrote(S)
+    return q
+
+
+def write_decode(view, qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, n_heads: int) -> torch.Tensor:
+    """One new token per sequence: split the packed qkv [B, 1, (H + 2 Hkv) hd], RoPE q and k at the sequence's
+    position (angle rows of the fp32 tables cos / sin [>= rows, hd / 2]), store k / v at that cache row; returns q
+    [B, H, hd].  An idle sequence of a per-sequence form stores nothing and gets a zero q row."""
+    what, sym = view.entry[WRITE_DECODE]
+    B, Hkv, hd, rows = view.check(what, None, False)
+    if qkv.numel() != B * (n_heads + 2 * Hkv) * hd:
+        raise ValueError(f"{what}: qkv {tuple(qkv.shape)} vs cache {tuple(view.cache[0].shape)}, B={B}, H={n_heads}")
+    return _write(what, sym, view, qkv, cos, sin, None, rows, (B, n_heads, Hkv), hd)
+
+
+def write_prefill(view, qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, n_heads: int) -> torch.Tensor:
+    """S new tokens per sequence: qkv [B, S, (H + 2 Hkv) hd]; token s is rotated at angle row pos + s and stored at
+    that cache row; returns q [B, S, H, hd].  A padding token (s >= n_b) stores nothing and gets a zero q row."""
+    what, sym = view.entry[WRITE_PREFILL]
+    if qkv.dim() != 3 or qkv.shape[1] < 1:
+        raise ValueError(f"{what}: qkv {tuple(qkv.shape)} must be [B, S >= 1, (H + 2 Hkv) hd]")
+    S = qkv.shape[1]
+    B, Hkv, hd, rows = view.check(what, S, False)
+    if qkv.shape[0] != B or qkv.shape[2] != (n_heads + 2 * Hkv) * hd:
+        raise ValueError(f"{what}: qkv {tuple(qkv.shape)} must be [B={B}, S, (H + 2 Hkv) hd] for cache "
+                         f"{tuple(view.cache[0].shape)}, H={n_heads}")
+    return _write(what, sym, view, qkv, cos, sin, S, rows, (B, S, n_heads, Hkv), hd)
+
+
+def _need_q(what: str, q, qs, ok: bool, lay: str, B: int, Hkv: int, hd: int) -> int:
+    """q of an attention launch, `lay` = [B, (S,) H, 128] bf16 contiguous (qs: its shape, `ok`: it fits); returns H."""
+    if hd != 128:
+        raise ValueError(f"{what}: head_dim 128 required, the cache has {hd}")
+    if not ok:
+        raise ValueError(f"{what}: q {tuple(qs)} must be {lay} with B = {B}")
+    H = qs[-2]
+    if H % Hkv or (H // Hkv) not in (1, 2, 4, 8):
+        raise ValueError(f"{what}: group size H / Hkv = {H} / {Hkv} must be 1, 2, 4 or 8")
+    if q.dtype is not _BF16:
+        raise ValueError(f"{what}: q must be bf16, got {q.dtype}")
+    if not q.is_contiguous():
+        raise ValueError(f"{what}: q must be contiguous (strides {q.stride()})")
+    return H
+
+
+def attend_decode(view, q: torch.Tensor, nsplit: Optional[int] = None) -> torch.Tensor:
+    """Grouped-query attention of one new token per sequence over cache rows 0 .. pos: q [B, H, 128] -> [B, H * 128].
+    The keys are split over `nsplit` workgroups per (batch, KV head) (flash-decoding; default: from the shapes alone,
+    enough to give the chip >= 256 workgroups, so a row's split does not depend on its position) and merged by a
+    combine kernel.  The row of an idle sequence is zero."""
+    what, sym = view.entry[ATTEND_DECODE]
+    B, Hkv, hd, rows = view.check(what, None, True)
+    qs = q.shape
+    H = _need_q(what, q, qs, len(qs) == 3 and qs[0] == B and qs[2] == hd, "[B, H, 128]", B, Hkv, hd)
+    if nsplit is None:
+        nsplit = max(1, min(8, -(-256 // (B * Hkv)), -(-rows // 64)))
+    elif not isinstance(nsplit, int) or isinstance(nsplit, bool) or nsplit < 1:
+        raise ValueError(f"{what}: nsplit={nsplit!r} must be None or an int >= 1")
+    names, index, geom, _ = view.args(None)
+    _need_cuda(what, (*index, q, *view.cache), names, ("q",), view.names)
+    out = torch.empty(B, H * hd, dtype=torch.bfloat16, device=q.device)
+    ws = torch.empty(B * Hkv * nsplit * (H // Hkv) * (hd + 2), dtype=torch.float32, device=q.device) \
+        if nsplit > 1 else None
+    _check(getattr(lib(), sym)(*map(_DATA_PTR, (q, *view.cache, *index, out)), None if ws is None else ws.data_ptr(),
+                               nsplit, B, H, Hkv, *geom, hd, C.c_float(hd ** -0.5), _stream()), what)
+    return out
+
+
+def attend_prefill(view, q: torch.Tensor) -> torch.Tensor:
+    """Causal grouped-query attention of S new tokens per sequence over the cache, which already holds their rows
+    (bf16 MFMA): q [B, S, H, 128] (RoPE applied); query s attends rows 0 .. pos + s.  Returns [B, S, H * 128] bf16,
+    rows s >= n_b zero.  No row past the last new one is read."""
+    what, sym = view.entry[ATTEND_PREFILL]
+    qs = q.shape
+    if len(qs) != 4 or qs[1] < 1:
+        raise ValueError(f"{what}: q {tuple(qs)} must be [B, S >= 1, H, 128]")
+    S = qs[1]
+    B, Hkv, hd, _ = view.check(what, S, True)
+    H = _need_q(what, q, qs, qs[0] == B and qs[3] == hd, "[B, S, H, 128]", B, Hkv, hd)
+    names, index, geom, tail = view.args(S)
+    _need_cuda(what, (*index, q, *view.cache), names, ("q",), view.names)
+    out = (torch.zeros if view.partial else torch.empty)(B, S, H * hd, dtype=torch.bfloat16, device=q.device)
+    _check(getattr(lib(), sym)(*map(_DATA_PTR, (q, *view.cache, *index, out)), B, S, H, Hkv, *geom, hd, *tail,
+                               C.c_float(hd ** -0.5), _stream()), what)
+    return out
+
+
+# The sixteen entry points by name: each builds the view of its form and calls the function of its operation.
+def qkv_rope_cache(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos_t: torch.Tensor, kc: torch.Tensor,
+                   vc: torch.Tensor, n_heads: int) -> torch.Tensor:
+    """One-token decode: split the packed qkv [B, 1, (H + 2 Hkv) hd], RoPE q and k
+    at the device position pos_t (int32 [1]), write k / v into the caches
+    [B, Hkv, C, hd] at that row, return q [B, H, hd].  No bounds check on the
+    device value: the caller keeps 0 <= pos < C."""
+    return write_decode(DenseUniform(kc, vc, pos_t), qkv, cos, sin, n_heads)
+
+
+def decode_attn(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, pos_t: torch.Tensor,
+                nsplit: Optional[int] = None) -> torch.Tensor:
+    """Grouped-query attention of one new token per sequence over cache rows
+    0..pos (pos_t int32 [1] on device): q [B, H, 128] -> [B, H * 128].  The keys
+    are split over `nsplit` workgroups per (batch, KV head) (flash-decoding,
+    default: enough to give the chip >= 256 workgroups) and merged by a combine
+    kernel.  Everything the kernel takes as a raw pointer is checked on the host
+    tensors before the library is touched, except the device value of pos_t:
+    reading it would force a sync inside a captured graph, so the caller keeps
+    0 <= pos (the kernel clamps pos + 1 to C)."""
+    return attend_decode(DenseUniform(kc, vc, pos_t), q, nsplit)
+
+
+def qkv_rope_cache_prefill(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: int, kc: torch.Tensor,
+                           vc: torch.Tensor, n_heads: int) -> torch.Tensor:
+    """S-token form of qkv_rope_cache with a host position: split the packed qkv
+    [B, S, (H + 2 Hkv) hd], RoPE q and k at angle rows pos + s, write k / v into
+    rows pos .. pos + S - 1 of the caches [B, Hkv, C, hd]; returns q [B, S, H, hd]."""
+    return write_prefill(DenseUniform(kc, vc, pos), qkv, cos, sin, n_heads)
+
+
+def prefill_attn(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, pos: int) -> torch.Tensor:
+    """Causal grouped-query attention of S new tokens over the static KV cache
+    (k_prefill_attn, bf16 MFMA): q [B, S, H, 128] (RoPE applied), caches
+    [B, Hkv, C, 128] already holding rows pos .. pos + S - 1; query s attends
+    cache rows 0 .. pos + s.  Returns [B, S, H * 128] bf16.  Rows >= pos + S of
+    the caches are never read."""
+    return attend_prefill(DenseUniform(kc, vc, pos), q)
+
+
+def qkv_rope_cache_seq(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos_t: torch.Tensor,
+                       kc: torch.Tensor, vc: torch.Tensor, n_heads: int) -> torch.Tensor:
+    """qkv_rope_cache with one device position per sequence (pos_t int32 [B]):
+    an active sequence gets the arithmetic of qkv_rope_cache at pos_t[b]; an
+    idle one writes nothing to its caches and its q row is zero."""
+    return write_decode(DenseSeq(kc, vc, pos_t), qkv, cos, sin, n_heads)
+
+
+def decode_attn_seq(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, pos_t: torch.Tensor,
+                    nsplit: Optional[int] = None) -> torch.Tensor:
+    """decode_attn with one device position per sequence (pos_t int32 [B]):
+    row b is bit-identical to decode_attn at pos = pos_t[b] with the same
+    nsplit; an idle sequence loads no cache row and its row is zero."""
+    return attend_decode(DenseSeq(kc, vc, pos_t), q, nsplit)
+
+
+def qkv_rope_cache_prefill_seq(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos_t: torch.Tensor,
+                               len_t: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor,
+                               n_heads: int) -> torch.Tensor:
+    """qkv_rope_cache_prefill with a device position and length per sequence
+    (int32 [B] each): token s < n_b of sequence b is rotated at angle row
+    pos_t[b] + s and written to that cache row; tokens s >= n_b write nothing
+    and their q rows are zero.  Returns q [B, S, H, hd]."""
+    return write_prefill(DenseSeq(kc, vc, pos_t, len_t), qkv, cos, sin, n_heads)
+
+
+def prefill_attn_seq(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, pos_t: torch.Tensor,
+                     len_t: torch.Tensor) -> torch.Tensor:
+    """prefill_attn with a device position and length per sequence (int32 [B]
+    each): q [B, S, H, 128] padded to the longest sequence; query s < n_b of
+    sequence b attends cache rows 0 .. pos_t[b] + s and its row is bit-identical
+    to prefill_attn on that sequence alone with (S = n_b, pos = pos_t[b]).  Rows
+    s >= n_b of the result are zero, their q rows are never loaded, and no cache
+    row past pos_t[b] + n_b - 1 is addressed.  Returns [B, S, H * 128] bf16."""
+    return attend_prefill(DenseSeq(kc, vc, pos_t, len_t), q)
+
+
+def qkv_rope_cache_paged(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos_t: torch.Tensor,
+                         table: torch.Tensor, kpool: torch.Tensor, vpool: torch.Tensor, n_heads: int) -> torch.Tensor:
+    """qkv_rope_cache_seq through a block table: an active sequence
+    (0 <= pos_t[b] < NP * page) gets the same q and writes the same k / v row,
+    into row pos_t[b] % page of page table[b, pos_t[b] // page]."""
+    return write_decode(Paged(kpool, vpool, table, pos_t), qkv, cos, sin, n_heads)
+
+
+def decode_attn_paged(q: torch.Tensor, kpool: torch.Tensor, vpool: torch.Tensor, table: torch.Tensor,
+                      pos_t: torch.Tensor, nsplit: Optional[int] = None) -> torch.Tensor:
+    """decode_attn_seq through a block table: row b is bit-identical to
+    decode_attn_seq on the dense cache of Cl = NP * page rows gathered from
+    sequence b's pages, with the same nsplit (default: from (B, Hkv, Cl))."""
+    return attend_decode(Paged(kpool, vpool, table, pos_t), q, nsplit)
+
+
+def qkv_rope_cache_prefill_paged(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos_t: torch.Tensor,
+                                 len_t: torch.Tensor, table: torch.Tensor, kpool: torch.Tensor, vpool: torch.Tensor,
+                                 n_heads: int) -> torch.Tensor:
+    """qkv_rope_cache_prefill_seq through a block table: token s < n_b of
+    sequence b (n_b from Cl = NP * page) is written to logical row pos_t[b] + s
+    of its pages.  Returns q [B, S, H, hd]."""
+    return write_prefill(Paged(kpool, vpool, table, pos_t, len_t), qkv, cos, sin, n_heads)
+
+
+def prefill_attn_paged(q: torch.Tensor, kpool: torch.Tensor, vpool: torch.Tensor, table: torch.Tensor,
+                       pos_t: torch.Tensor, len_t: torch.Tensor) -> torch.Tensor:
+    """prefill_attn_seq through a block table: rows s < n_b of sequence b are
+    bit-identical to prefill_attn_seq on the dense cache gathered from its
+    pages; no row past pos_t[b] + n_b - 1 is addressed, through any page.
+    Returns [B, S, H * 128] bf16, rows s >= n_b zero."""
+    return attend_prefill(Paged(kpool, vpool, table, pos_t, len_t), q)
 
 
 def qkv_rope_cache_paged_kv8(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos_t: torch.Tensor,
@@ -701,22 +668,7 @@ def qkv_rope_cache_paged_kv8(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Te
     """qkv_rope_cache_paged over an fp8 cache: the same q; the k / v row the bf16
     kernel would have stored goes through kv8_quant_ref into the code pools and
     the scales, at the same page and page row."""
-    what = "qkv_rope_cache_paged_kv8"
-    B, NP, P, Hkv, page, hd = _need_paged_kv8(what, kpool8, vpool8, kscale, vscale, table)
-    Cl = NP * page
-    _need_seq(what, B, pos_t=pos_t)
-    _need(qkv, f"{what} qkv")
-    if qkv.numel() != B * (n_heads + 2 * Hkv) * hd or cos.dim() != 2 or cos.shape[-1] * 2 != hd:
-        raise ValueError(f"{what}: qkv {tuple(qkv.shape)} vs pools {tuple(kpool8.shape)}, B={B}, H={n_heads}")
-    if cos.shape[0] < Cl or sin.shape != cos.shape or cos.dtype != torch.float32 or sin.dtype != torch.float32 \
-            or not (cos.is_cuda and sin.is_cuda and cos.is_contiguous() and sin.is_contiguous()):
-        raise ValueError(f"{what}: rope tables {tuple(cos.shape)} {cos.dtype} must be contiguous fp32 CUDA tensors "
-                         f"covering NP * page = {Cl} rows")
-    q = torch.empty(B, n_heads, hd, dtype=torch.bfloat16, device=qkv.device)
-    _check(lib().gpbs_hip_qkv_rope_cache_paged_kv8(_ptr(qkv), _ptr(cos), _ptr(sin), _ptr(pos_t), _ptr(table), _ptr(q),
-                                                   _ptr(kpool8), _ptr(vpool8), _ptr(kscale), _ptr(vscale), B, n_heads,
-                                                   Hkv, NP, P, page, hd, _stream()), what)
-    return q
+    return write_decode(PagedKv8(kpool8, vpool8, kscale, vscale, table, pos_t), qkv, cos, sin, n_heads)
 
 
 def decode_attn_paged_kv8(q: torch.Tensor, kpool8: torch.Tensor, vpool8: torch.Tensor, kscale: torch.Tensor,
@@ -725,29 +677,7 @@ def decode_attn_paged_kv8(q: torch.Tensor, kpool8: torch.Tensor, vpool8: torch.T
     """decode_attn_paged over an fp8 cache: bit-identical to decode_attn_paged on
     the bf16 pools kv8_dequant(kpool8, kscale) / kv8_dequant(vpool8, vscale) with
     the same nsplit (default: from (B, Hkv, Cl))."""
-    what = "decode_attn_paged_kv8"
-    B, NP, P, Hkv, page, hd = _need_paged_kv8(what, kpool8, vpool8, kscale, vscale, table)
-    Cl = NP * page
-    if q.dim() != 3 or q.shape[0] != B or q.shape[2] != hd:
-        raise ValueError(f"{what}: q {tuple(q.shape)} must be [B={B}, H, 128]")
-    H = q.shape[1]
-    if H % Hkv or (H // Hkv) not in (1, 2, 4, 8):
-        raise ValueError(f"{what}: group size H / Hkv = {H} / {Hkv} must be 1, 2, 4 or 8")
-    if q.dtype != torch.bfloat16 or not q.is_contiguous():
-        raise ValueError(f"{what}: q must be contiguous bf16, got {q.dtype} strides {q.stride()}")
-    if nsplit is not None and (not isinstance(nsplit, int) or isinstance(nsplit, bool) or nsplit < 1):
-        raise ValueError(f"{what}: nsplit={nsplit!r} must be None or an int >= 1")
-    _need_seq(what, B, pos_t=pos_t)
-    _need(q, f"{what} q")
-    out = torch.empty(B, H * hd, dtype=torch.bfloat16, device=q.device)
-    if nsplit is None:  # as decode_attn_paged
-        nsplit = max(1, min(8, -(-256 // (B * Hkv)), -(-Cl // 64)))
-    ws = torch.empty(B * Hkv * nsplit * (H // Hkv) * (hd + 2), dtype=torch.float32, device=q.device) \
-        if nsplit > 1 else None
-    _check(lib().gpbs_hip_decode_attn_paged_kv8(_ptr(q), _ptr(kpool8), _ptr(vpool8), _ptr(kscale), _ptr(vscale),
-                                                _ptr(pos_t), _ptr(table), _ptr(out), _ptr(ws), nsplit, B, H, Hkv, NP,
-                                                P, page, hd, C.c_float(hd ** -0.5), _stream()), what)
-    return out
+    return attend_decode(PagedKv8(kpool8, vpool8, kscale, vscale, table, pos_t), q, nsplit)
 
 
 def qkv_rope_cache_prefill_paged_kv8(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos_t: torch.Tensor,
@@ -757,30 +687,7 @@ def qkv_rope_cache_prefill_paged_kv8(qkv: torch.Tensor, cos: torch.Tensor, sin: 
     """qkv_rope_cache_prefill_paged over an fp8 cache: the same q; every k / v row
     the bf16 kernel would have stored goes through kv8_quant_ref into the code
     pools and the scales.  Returns q [B, S, H, hd]."""
-    what = "qkv_rope_cache_prefill_paged_kv8"
-    B, NP, P, Hkv, page, hd = _need_paged_kv8(what, kpool8, vpool8, kscale, vscale, table)
-    Cl = NP * page
-    if qkv.dim() != 3 or qkv.shape[0] != B or qkv.shape[1] < 1 or qkv.shape[2] != (n_heads + 2 * Hkv) * hd \
-            or cos.dim() != 2 or cos.shape[-1] * 2 != hd:
-        raise ValueError(f"{what}: qkv {tuple(qkv.shape)} must be [B={B}, S, (H + 2 Hkv) hd] for pools "
-                         f"{tuple(kpool8.shape)}, H={n_heads}, rope tables {tuple(cos.shape)}")
-    S = qkv.shape[1]
-    _need_seq(what, B, pos_t=pos_t, len_t=len_t)
-    if cos.shape[0] < Cl or sin.shape != cos.shape or cos.dtype != torch.float32 or sin.dtype != torch.float32 \
-            or not (cos.is_contiguous() and sin.is_contiguous()):
-        raise ValueError(f"{what}: rope tables {tuple(cos.shape)} {cos.dtype} must be contiguous fp32 and cover "
-                         f"NP * page = {Cl} rows")
-    if qkv.dtype != torch.bfloat16 or not qkv.is_contiguous():
-        raise ValueError(f"{what}: qkv must be contiguous bf16, got {qkv.dtype} strides {qkv.stride()}")
-    _need(qkv, f"{what} qkv")
-    if not (cos.is_cuda and sin.is_cuda):
-        raise ValueError(f"{what}: rope tables must be CUDA tensors")
-    q = torch.empty(B, S, n_heads, hd, dtype=torch.bfloat16, device=qkv.device)
-    _check(lib().gpbs_hip_qkv_rope_cache_prefill_paged_kv8(_ptr(qkv), _ptr(cos), _ptr(sin), _ptr(pos_t), _ptr(len_t),
-                                                           _ptr(table), _ptr(q), _ptr(kpool8), _ptr(vpool8),
-                                                           _ptr(kscale), _ptr(vscale), B, S, n_heads, Hkv, NP, P,
-                                                           page, hd, _stream()), what)
-    return q
+    return write_prefill(PagedKv8(kpool8, vpool8, kscale, vscale, table, pos_t, len_t), qkv, cos, sin, n_heads)
 
 
 def prefill_attn_paged_kv8(q: torch.Tensor, kpool8: torch.Tensor, vpool8: torch.Tensor, kscale: torch.Tensor,
@@ -789,29 +696,7 @@ def prefill_attn_paged_kv8(q: torch.Tensor, kpool8: torch.Tensor, vpool8: torch.
     """prefill_attn_paged over an fp8 cache: bit-identical to prefill_attn_paged
     on the bf16 pools kv8_dequant(kpool8, kscale) / kv8_dequant(vpool8, vscale).
     Returns [B, S, H * 128] bf16, rows s >= n_b zero."""
-    what = "prefill_attn_paged_kv8"
-    B, NP, P, Hkv, page, hd = _need_paged_kv8(what, kpool8, vpool8, kscale, vscale, table)
-    if q.dim() != 4 or q.shape[0] != B or q.shape[1] < 1 or q.shape[3] != hd:
-        raise ValueError(f"{what}: q {tuple(q.shape)} must be [B={B}, S, H, 128]")
-    S, H = q.shape[1], q.shape[2]
-    if H % Hkv or (H // Hkv) not in (1, 2, 4, 8):
-        raise ValueError(f"{what}: group size H / Hkv = {H} / {Hkv} must be 1, 2, 4 or 8")
-    if q.dtype != torch.bfloat16 or not q.is_contiguous():
-        raise ValueError(f"{what}: q must be contiguous bf16, got {q.dtype} strides {q.stride()}")
-    _need_seq(what, B, pos_t=pos_t, len_t=len_t)
-    _need(q, f"{what} q")
-    out = torch.zeros(B, S, H * hd, dtype=torch.bfloat16, device=q.device)  # the kernel stores rows < n_b only
-    _check(lib().gpbs_hip_prefill_attn_paged_kv8(_ptr(q), _ptr(kpool8), _ptr(vpool8), _ptr(kscale), _ptr(vscale),
-                                                 _ptr(pos_t), _ptr(len_t), _ptr(table), _ptr(out), B, S, H, Hkv, NP,
-                                                 P, page, hd, C.c_float(hd ** -0.5), _stream()), what)
-    return out
-
-
-def attn_paged_kv8_ref(q: torch.Tensor, kpool8: torch.Tensor, vpool8: torch.Tensor, kscale: torch.Tensor,
-                       vscale: torch.Tensor, table, pos, lens) -> torch.Tensor:
-    """Plain-torch reference of the two _kv8 attention kernels: attn_paged_ref
-    over the dequantised pools."""
-    return attn_paged_ref(q, kv8_dequant(kpool8, kscale), kv8_dequant(vpool8, vscale), table, pos, lens)
+    return attend_prefill(PagedKv8(kpool8, vpool8, kscale, vscale, table, pos_t, len_t), q)
 
 
 # --------------------------------------------------------------------------- fp8 (config #5, CDNA4 fp8 MFMA)
