@@ -23,10 +23,14 @@
 // global SOURCE address, LDS is written lane-linear).  One MFMA per 16x16
 // block per K-tile: 16 per wave per K-tile.
 //
-// Operand lane map: lane l holds row / column (l & 15) and the 32
+// Operand fragments: lane l holds row / column (l & 15) and the 32
 // consecutive k bytes from 32 * (l >> 4): two ds_read_b128 per fragment
 // (chunks 2g and 2g + 1, g = l >> 4).  A and B fragments are built the same
-// way, so each lane group pairs the same 32 k's of both operands.
+// way, so each lane group pairs the same 32 k's of both operands and the sum
+// is right whatever k the hardware gives each byte.  The instruction's own
+// map of an e4m3 operand is not this one (fp4_kernels.hip measured it:
+// VGPRs 0..3 are k = 16 g .. + 16, VGPRs 4..7 k = 64 + 16 g .. + 16); it
+// matters only where the two operands differ in format or carry real scales.
 //
 // Ragged M: any M > 0.  Staging clamps the row index to M - 1 (the clamped
 // rows feed only accumulators whose stores are skipped), rows >= M are not

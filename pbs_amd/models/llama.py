@@ -174,6 +174,23 @@ class Block(nn.Module):
             "w2": llm.Fp8Weight(self.w2.weight),
         }
 
+    def attach_mxfp4(self, emulate: bool = False):
+        """The four packed weights of attach_fp8 as MXFP4 (llm.Mxfp4Weight: e2m1
+        codes, one E8M0 scale per 32 k, 4.25 bits per weight); forward_fp8 and
+        decode_fp8_static then run the fp4 linear.  ``emulate``: the oracle,
+        Fp8Weight copies that hold exactly the dequantised MX weights, for the
+        stock fp8 kernels (ValueError if a row's block exponents do not fit one
+        e4m3 row scale)."""
+        from ..ops import llm
+        # _fp8 keeps its name from attach_fp8: the packed weights of the fp8 activation path, by linear; a value is
+        # an Fp8Weight or an Mxfp4Weight, and llm.linear_q picks the kernel by that type
+        self._fp8 = {}
+        for name, w in (("qkv", torch.cat([self.wq.weight, self.wk.weight, self.wv.weight], 0)),
+                        ("o", self.wo.weight), ("w13", torch.cat([self.w1.weight, self.w3.weight], 0)),
+                        ("w2", self.w2.weight)):
+            mx = llm.Mxfp4Weight(w)
+            self._fp8[name] = llm.mxfp4_as_fp8(mx) if emulate else mx
+
     def forward_fp8(self, x, cos, sin, cache, pos: int, tiled: bool = False, view=None):
         """Decode/prefill block on fp8 weights (fp8 MFMA linears + fused gfx950
         RMSNorm/RoPE/SwiGLU); inference only.  ``tiled``: the linears run the
@@ -187,8 +204,7 @@ class Block(nn.Module):
         from ..ops import llm
         cfg, hd, f = self.cfg, self.cfg.head_dim, self._fp8
         B, S, _ = x.shape
-        qkv = llm.fp8_linear_q(*llm.rmsnorm_quant_fp8(x, self.attn_norm.weight, self.attn_norm.eps), f["qkv"],
-                               tiled=tiled)
+        qkv = llm.linear_q(*llm.rmsnorm_quant_fp8(x, self.attn_norm.weight, self.attn_norm.eps), f["qkv"], tiled=tiled)
         nq, nkv = cfg.n_heads * hd, cfg.n_kv_heads * hd
         if view is not None:
             o = llm.attend_prefill(view, llm.write_prefill(view, qkv, cos, sin, cfg.n_heads))
@@ -203,10 +219,9 @@ class Block(nn.Module):
             o = F.scaled_dot_product_attention(q.transpose(1, 2), kc[:, :, :pos + S], vc[:, :, :pos + S],
                                                is_causal=(S > 1), enable_gqa=True)
             o = o.transpose(1, 2).reshape(B, S, nq)
-        x = x + llm.fp8_linear(o, f["o"], tiled=tiled)
-        gu = llm.fp8_linear_q(*llm.rmsnorm_quant_fp8(x, self.mlp_norm.weight, self.mlp_norm.eps), f["w13"],
-                              tiled=tiled)
-        return x + llm.fp8_linear_q(*llm.swiglu_quant_fp8(gu), f["w2"], tiled=tiled)
+        x = x + llm.linear_q(*llm.quant_rows_fp8(o), f["o"], tiled=tiled)
+        gu = llm.linear_q(*llm.rmsnorm_quant_fp8(x, self.mlp_norm.weight, self.mlp_norm.eps), f["w13"], tiled=tiled)
+        return x + llm.linear_q(*llm.swiglu_quant_fp8(gu), f["w2"], tiled=tiled)
 
     def decode_fp8_static(self, x, cos, sin, cache, pos_i32, pos_i64, mask, view=None):
         """One-token decode with every shape static and the position on device
@@ -223,13 +238,13 @@ class Block(nn.Module):
         cfg, hd, f = self.cfg, self.cfg.head_dim, self._fp8
         B = x.shape[0]
         G = cfg.n_heads // cfg.n_kv_heads
-        qkv = llm.fp8_linear_q(*llm.rmsnorm_quant_fp8(x, self.attn_norm.weight, self.attn_norm.eps), f["qkv"])
+        qkv = llm.linear_q(*llm.rmsnorm_quant_fp8(x, self.attn_norm.weight, self.attn_norm.eps), f["qkv"])
         nq, nkv = cfg.n_heads * hd, cfg.n_kv_heads * hd
         if view is not None:
             o = llm.attend_decode(view, llm.write_decode(view, qkv, cos, sin, cfg.n_heads))
-            x = llm.fp8_linear_q(*llm.quant_rows_fp8(o.view(B, 1, nq)), f["o"], resid=x)
-            gu = llm.fp8_linear_q(*llm.rmsnorm_quant_fp8(x, self.mlp_norm.weight, self.mlp_norm.eps), f["w13"])
-            return llm.fp8_linear_q(*llm.swiglu_quant_fp8(gu), f["w2"], resid=x)
+            x = llm.linear_q(*llm.quant_rows_fp8(o.view(B, 1, nq)), f["o"], resid=x)
+            gu = llm.linear_q(*llm.rmsnorm_quant_fp8(x, self.mlp_norm.weight, self.mlp_norm.eps), f["w13"])
+            return llm.linear_q(*llm.swiglu_quant_fp8(gu), f["w2"], resid=x)
         kc, vc = cache
         q = llm.rope_dpos(qkv[..., :nq].reshape(B, 1, cfg.n_heads, hd), cos, sin, pos_i32)
         k = llm.rope_dpos(qkv[..., nq:nq + nkv].reshape(B, 1, cfg.n_kv_heads, hd), cos, sin, pos_i32)
@@ -239,9 +254,9 @@ class Block(nn.Module):
         qg = q.view(B, cfg.n_kv_heads, G, hd)
         sc = torch.matmul(qg, kc.transpose(-1, -2)).float() * (hd ** -0.5) + mask
         o = torch.matmul(torch.softmax(sc, -1).to(vc.dtype), vc)  # [B, Hkv, G, hd]
-        x = x + llm.fp8_linear(o.reshape(B, 1, nq), f["o"])
-        gu = llm.fp8_linear_q(*llm.rmsnorm_quant_fp8(x, self.mlp_norm.weight, self.mlp_norm.eps), f["w13"])
-        return x + llm.fp8_linear_q(*llm.swiglu_quant_fp8(gu), f["w2"])
+        x = x + llm.linear_q(*llm.quant_rows_fp8(o.reshape(B, 1, nq)), f["o"])
+        gu = llm.linear_q(*llm.rmsnorm_quant_fp8(x, self.mlp_norm.weight, self.mlp_norm.eps), f["w13"])
+        return x + llm.linear_q(*llm.swiglu_quant_fp8(gu), f["w2"])
 
     def forward(self, x, cos, sin, cache=None, pos: int = 0, fused: bool = False, prefill_attn: bool = False,
                 seq=None, kv8: bool = False):
@@ -290,6 +305,15 @@ class Llama(nn.Module):
         from ..ops import llm
         for layer in self.layers:
             layer.attach_fp8()
+        self._fp8_head = llm.Fp8Weight(self.lm_head.weight)
+        return self
+
+    def attach_mxfp4(self, emulate: bool = False):
+        """MXFP4 copies of every block linear (Block.attach_mxfp4); the LM head
+        stays fp8 (e4m3fn)."""
+        from ..ops import llm
+        for layer in self.layers:
+            layer.attach_mxfp4(emulate=emulate)
         self._fp8_head = llm.Fp8Weight(self.lm_head.weight)
         return self
 
@@ -395,7 +419,19 @@ class LlamaDecoder:
                  fused: Optional[bool] = None, fp8: bool = False, graph: bool = False, static: bool = False,
                  prefill_tiled: bool = False, prefill_attn: bool = False, ragged: bool = False,
                  paged: bool = False, pages: Optional[int] = None, page: int = 64, kv_fp8=False,
-                 sampling: bool = False):
+                 sampling: bool = False, w4=False):
+        # opt-in (needs fp8=True): the four block linears of every layer stream MXFP4 weights (ops.llm.Mxfp4Weight:
+        # e2m1 codes and one E8M0 scale per 32 k, 4.25 bits per weight where fp8 stores 8) through the fp4 MFMA
+        # linear; the LM head stays fp8.  Every mode on top (prefill, chunks, ragged, paged, kv_fp8, sampling, admit,
+        # the static step and its graph) runs unchanged.  "emulate": the oracle of the former, the stock fp8
+        # kernels over Fp8Weight copies that hold exactly the dequantised MX weights.
+        if not (w4 is False or w4 is True or w4 == "emulate"):
+            raise ValueError(f"LlamaDecoder: w4 {w4!r} must be False, True or 'emulate'")
+        if w4 and not fp8:
+            raise ValueError("LlamaDecoder: w4 runs on the fp8 path (needs fp8=True)")
+        if w4 is True and prefill_tiled:
+            raise ValueError("LlamaDecoder: w4=True with prefill_tiled=True: there is no tiled fp4 GEMM")
+        self.w4 = w4
         # opt-in (implies ragged): the KV cache is a pool of `pages` pages of
         # `page` rows per layer, [pages, Hkv, page, hd], and one block table
         # [batch, ceil(context / page)] for all layers maps every slot's logical
@@ -473,7 +509,10 @@ class LlamaDecoder:
         self.prefill_tiled = prefill_tiled
         if fp8:  # weights streamed as e4m3fn through the fp8 MFMA linears (half the bytes of bf16)
             with torch.no_grad():
-                self.model.attach_fp8()
+                if w4:
+                    self.model.attach_mxfp4(emulate=(w4 == "emulate"))
+                else:
+                    self.model.attach_fp8()
         if (graph or static) and not fp8:
             raise ValueError("static-shape / graph decode is the fp8 path (needs fp8=True)")
         self.graph = graph

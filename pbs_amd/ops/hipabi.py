@@ -83,6 +83,9 @@ def bind(lib):
     _p(lib, "gpbs_hip_fp8_set_opts", C.c_int, C.c_int)
     _p(lib, "gpbs_hip_fp8_linear_res", C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp)
     _p(lib, "gpbs_hip_fp8_linear", C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp)
+    # the fp8 linears over an MXFP4 weight: the E8M0 block scales (uint8 [N, K / 32]) in place of sw
+    _p(lib, "gpbs_hip_mxfp4_linear_res", C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp)
+    _p(lib, "gpbs_hip_mxfp4_linear", C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp)
     _p(lib, "gpbs_hip_rope_bf16_dpos", C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp)
     _p(lib, "gpbs_hip_qkv_rope_cache", C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int,
        C.c_int, vp)

@@ -889,6 +889,236 @@ def fp8_linear_ref(x: torch.Tensor, w: Fp8Weight) -> torch.Tensor:
     return (acc * sx.unsqueeze(1) * w.s.float().unsqueeze(0)).view(*x.shape[:-1], w.N)
 
 
+# --------------------------------------------------------------------------- MXFP4 weights (csrc/hip/fp4_kernels.hip)
+# OCP MXFP4: e2m1 codes (1 sign, 2 exponent, 1 mantissa bit; magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6), two per byte
+# with the even k in the low nibble, and one E8M0 scale byte per 32 consecutive k of a row, value 2^(byte - 127);
+# no per-row scale.  4.25 bits per weight.
+MXFP4_BLOCK = 32
+MXFP4_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)  # by the low three bits of a code; bit 3 is the sign
+
+
+def mxfp4_quant_ref(w: torch.Tensor):
+    """The MXFP4 quantiser of the OCP MX specification, plain torch on any device:
+    w [N, K] (K % 32 == 0) of finite bf16 values -> (codes uint8 [N, K / 2], scales
+    uint8 [N, K / 32]).  Per block of 32: amax = max |v|, E = floor(log2 amax) - 2
+    clamped to [-127, 127] (0 for an all-zero block), byte = E + 127, and every
+    element is v 2^-E (exact in fp32) rounded to the nearest e2m1 value, ties to
+    the even code, saturating at +-6.  The exponent comes from the bits of amax
+    and the rounding is seven comparisons with exact constants, so CPU and GPU
+    give the same bits.  inf, NaN and bf16 subnormals are outside the contract.
+    Requantising dequant() gives the same codes and scales back (a block's
+    largest code is a 4 or a 6, which names the same E), except where
+    0.5 * 2^E is no bf16 normal."""
+    N, K = w.shape
+    if K % MXFP4_BLOCK:
+        raise ValueError(f"mxfp4_quant_ref: K={K} must be a multiple of {MXFP4_BLOCK}")
+    v = w.detach().to(torch.bfloat16).float().reshape(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    amax = v.abs().amax(-1)
+    e = ((amax.view(torch.int32) >> 23) - 127 - 2).clamp(-127, 127)  # the biased exponent field is floor(log2 amax) + 127
+    e = torch.where(amax > 0, e, torch.zeros_like(e))
+    inv = ((127 - e) << 23).to(torch.int32).view(torch.float32)  # 2^-E, E in [-127, 125] for bf16 input
+    t = v * inv.unsqueeze(-1)
+    a = t.abs()
+    # the midpoints of adjacent magnitudes; the tie goes to the even code: up at 0.75, 1.75, 3.5, down at the others
+    mag = ((a > 0.25).to(torch.uint8) + (a >= 0.75) + (a > 1.25) + (a >= 1.75) + (a > 2.5) + (a >= 3.5) + (a > 5.0))
+    code = (mag | ((v.view(torch.int32) >> 28) & 8).to(torch.uint8)).reshape(N, K // 2, 2)
+    return (code[..., 0] | (code[..., 1] << 4)).contiguous(), (e + 127).to(torch.uint8)
+
+
+def _e8m0_value(b: torch.Tensor) -> torch.Tensor:
+    """2^(byte - 127) as fp32 (byte 0 is the fp32 subnormal 2^-127)."""
+    i = b.to(torch.int32)
+    return torch.where(i > 0, i << 23, torch.full_like(i, 0x00400000)).view(torch.float32)
+
+
+class Mxfp4Weight:
+    """A linear weight [N, K] stored as OCP MXFP4: e2m1 codes and one E8M0 scale
+    byte per 32 k of a row, both in the lane order of k_mxfp4_gemm_skinny."""
+
+    def __init__(self, w: torch.Tensor):
+        w = w.detach().to(torch.bfloat16).contiguous()
+        if w.dim() != 2 or w.shape[0] % 16 or w.shape[1] % 256:
+            raise ValueError(f"Mxfp4Weight: {tuple(w.shape)} needs [N, K] with N % 16 == 0 and K % 256 == 0")
+        self._store(*mxfp4_quant_ref(w))
+
+    @classmethod
+    def from_quantised(cls, codes: torch.Tensor, scales: torch.Tensor) -> "Mxfp4Weight":
+        """The weight of given row-major data (no quantiser involved): codes uint8
+        [N, K / 2], the even k in the low nibble, and scales uint8 [N, K / 32],
+        none of them 0xFF (the NaN of E8M0)."""
+        if codes.dtype != torch.uint8 or codes.dim() != 2:
+            raise ValueError(f"Mxfp4Weight.from_quantised: codes must be uint8 [N, K / 2], got {codes.dtype} "
+                             f"{tuple(codes.shape)}")
+        N, K = codes.shape[0], 2 * codes.shape[1]
+        if N % 16 or K % 256 or N == 0 or K == 0:
+            raise ValueError(f"Mxfp4Weight: [N={N}, K={K}] needs N % 16 == 0 and K % 256 == 0")
+        if scales.dtype != torch.uint8 or tuple(scales.shape) != (N, K // MXFP4_BLOCK) or scales.device != codes.device:
+            raise ValueError(f"Mxfp4Weight.from_quantised: scales must be uint8 [{N}, {K // MXFP4_BLOCK}] on "
+                             f"{codes.device}, got {scales.dtype} {tuple(scales.shape)} on {scales.device}")
+        if bool((scales == 0xFF).any()):
+            raise ValueError("Mxfp4Weight.from_quantised: a scale byte is 0xFF (NaN in E8M0)")
+        self = cls.__new__(cls)
+        self._store(codes.contiguous(), scales.contiguous())
+        return self
+
+    def _store(self, codes: torch.Tensor, scales: torch.Tensor):
+        self.N, self.K = codes.shape[0], 2 * codes.shape[1]
+        self.qs = self.shuffle(codes)  # the only stored copies: the kernel's lane-order layouts
+        self.ss = self.shuffle_scales(scales)
+
+    # Kernel layout of the codes: [N/16 strips][K/256 blocks][2 steps u][4 lane groups g][16 rows r][16 B];
+    # lane l = 16 g + r of the wave that owns (strip, block) reads the 16 bytes (32 codes, one MX block)
+    # W[16 strip + r][256 block + 128 u + 32 g : +32] at step u, so each load instruction is one
+    # contiguous 1 KiB run.
+    def shuffle(self, codes: torch.Tensor) -> torch.Tensor:
+        b = codes.view(self.N // 16, 16, self.K // 256, 2, 4, 16)
+        return b.permute(0, 2, 3, 4, 1, 5).contiguous().view(self.N, self.K // 2)
+
+    # Kernel layout of the scales: [N/16 strips][K/256 blocks][4 lane groups g][16 rows r][2 steps u]; lane
+    # l = 16 g + r reads one 2-byte word per block, byte u the scale of its codes at step u (MX block
+    # 8 block + 4 u + g of row 16 strip + r), so each load instruction is one contiguous 128-byte run.
+    def shuffle_scales(self, scales: torch.Tensor) -> torch.Tensor:
+        b = scales.view(self.N // 16, 16, self.K // 256, 2, 4)
+        return b.permute(0, 2, 4, 1, 3).contiguous().view(self.N, self.K // MXFP4_BLOCK)
+
+    @property
+    def codes(self) -> torch.Tensor:
+        """Row-major [N, K / 2] uint8 (a copy; for references and tests)."""
+        b = self.qs.view(self.N // 16, self.K // 256, 2, 4, 16, 16)
+        return b.permute(0, 4, 1, 2, 3, 5).contiguous().view(self.N, self.K // 2)
+
+    @property
+    def scales(self) -> torch.Tensor:
+        """Row-major [N, K / 32] uint8 (a copy)."""
+        b = self.ss.view(self.N // 16, self.K // 256, 4, 16, 2)
+        return b.permute(0, 3, 1, 4, 2).contiguous().view(self.N, self.K // MXFP4_BLOCK)
+
+    def dequant(self) -> torch.Tensor:
+        """fp32 [N, K] of value(code) * 2^(byte - 127): exact (one significant bit
+        pair times a power of two) wherever that is a finite fp32."""
+        c = self.codes
+        nib = torch.stack([c & 0xF, c >> 4], -1).view(self.N, self.K).long()
+        lut = torch.tensor(MXFP4_VALUES + tuple(-x for x in MXFP4_VALUES), dtype=torch.float32, device=c.device)
+        return (lut[nib].view(self.N, -1, MXFP4_BLOCK) * _e8m0_value(self.scales).unsqueeze(-1)).view(self.N, self.K)
+
+    def nbytes(self) -> int:
+        return self.qs.numel() + self.ss.numel()
+
+
+def mxfp4_shuffled_offset(n: int, k: int, K: int) -> int:
+    """Byte offset in ``Mxfp4Weight.qs`` of the 16 bytes holding the codes
+    W[n][k : k + 32] (k % 32 == 0); the Python twin of the weight address of
+    k_mxfp4_gemm_skinny (csrc/hip/fp4_kernels.hip)."""
+    if k % 32 or K % 256 or not 0 <= k < K:
+        raise ValueError(f"mxfp4_shuffled_offset: k={k} (k % 32 == 0, 0 <= k < K), K={K} (K % 256 == 0)")
+    return ((n // 16) * (K // 256) + k // 256) * 2048 + ((k % 256) // 128) * 1024 + ((k % 128) // 32) * 256 \
+        + (n % 16) * 16
+
+
+def mxfp4_scale_offset(n: int, k: int, K: int) -> int:
+    """Byte offset in ``Mxfp4Weight.ss`` of the scale of the MX block that holds
+    W[n][k]; the twin of the scale address of k_mxfp4_gemm_skinny."""
+    if K % 256 or not 0 <= k < K:
+        raise ValueError(f"mxfp4_scale_offset: k={k} (0 <= k < K), K={K} (K % 256 == 0)")
+    return ((n // 16) * (K // 256) + k // 256) * 128 + (((k % 128) // 32) * 16 + n % 16) * 2 + (k % 256) // 128
+
+
+def mxfp4_linear_q(xq: torch.Tensor, sx: torch.Tensor, w: Mxfp4Weight,
+                   resid: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y = (xq @ deq(W)^T) * sx[m] (+ resid, fused into the epilogue) on
+    already-quantised e4m3 rows, as fp8_linear_q; bf16 out.  M > 64 without a
+    residual runs one launch per 64 rows.  The library takes raw pointers, so
+    everything it reads is checked here first."""
+    lead = xq.shape[:-1]
+    if xq.dtype != torch.float8_e4m3fn or xq.shape[-1] != w.K or not xq.is_contiguous():
+        raise ValueError(f"mxfp4_linear_q: need contiguous e4m3fn [..., {w.K}], got {xq.dtype} {tuple(xq.shape)}")
+    M = xq.numel() // w.K
+    if M == 0:
+        raise ValueError(f"mxfp4_linear_q: xq {tuple(xq.shape)} has no rows")
+    if sx.dtype != torch.float32 or not sx.is_contiguous() or sx.numel() != M:
+        raise ValueError(f"mxfp4_linear_q: sx must be contiguous fp32 with {M} elements, got {sx.dtype} "
+                         f"{tuple(sx.shape)} contiguous={sx.is_contiguous()}")
+    if resid is not None and (resid.dtype != torch.bfloat16 or not resid.is_contiguous()
+                              or resid.numel() != M * w.N):
+        raise ValueError(f"mxfp4_linear_q: resid must be contiguous bf16 with {M} x {w.N} elements, got "
+                         f"{resid.dtype} {tuple(resid.shape)} contiguous={resid.is_contiguous()}")
+    if w.qs.dtype != torch.uint8 or w.qs.numel() != w.N * w.K // 2 or not w.qs.is_contiguous() \
+            or w.ss.dtype != torch.uint8 or w.ss.numel() != w.N * w.K // MXFP4_BLOCK or not w.ss.is_contiguous():
+        raise ValueError(f"mxfp4_linear_q: weight [{w.N}, {w.K}] with codes {w.qs.dtype} {tuple(w.qs.shape)}, scales "
+                         f"{w.ss.dtype} {tuple(w.ss.shape)}")
+    for name, t in (("xq", xq), ("sx", sx), ("weight", w.qs), ("weight scale", w.ss), ("resid", resid)):
+        if t is not None and not t.is_cuda:
+            raise ValueError(f"mxfp4_linear_q: {name} must be a CUDA tensor, got {t.device}")
+        if t is not None and t.device != xq.device:
+            raise ValueError(f"mxfp4_linear_q: {name} is on {t.device}, xq on {xq.device}")
+    if resid is not None and M > FP8_M_TILE:
+        raise ValueError(f"mxfp4_linear_q: resid {tuple(resid.shape)} for [{M}, {w.N}] (M <= {FP8_M_TILE})")
+    y = torch.empty(*lead, w.N, dtype=torch.bfloat16, device=xq.device)
+    L, st = lib(), _stream()
+    if resid is not None:
+        _check(L.gpbs_hip_mxfp4_linear_res(_ptr(xq), _ptr(sx), _ptr(w.qs), _ptr(w.ss), _ptr(y), _ptr(resid), M, w.N,
+                                           w.K, st), "mxfp4_linear_res")
+        return y
+    if M <= FP8_M_TILE:
+        _check(L.gpbs_hip_mxfp4_linear(_ptr(xq), _ptr(sx), _ptr(w.qs), _ptr(w.ss), _ptr(y), M, w.N, w.K, st),
+               "mxfp4_linear")
+        return y
+    x2, s2, y2 = xq.view(M, w.K), sx.reshape(M), y.view(M, w.N)
+    for m0 in range(0, M, FP8_M_TILE):
+        m1 = min(M, m0 + FP8_M_TILE)
+        _check(L.gpbs_hip_mxfp4_linear(_ptr(x2[m0:m1]), _ptr(s2[m0:m1]), _ptr(w.qs), _ptr(w.ss), _ptr(y2[m0:m1]),
+                                       m1 - m0, w.N, w.K, st), "mxfp4_linear")
+    return y
+
+
+def mxfp4_linear(x: torch.Tensor, w: Mxfp4Weight) -> torch.Tensor:
+    """y = x @ deq(W)^T with x [..., K] bf16 quantised per token to fp8 on the fly."""
+    xq, sx = quant_rows_fp8(x)
+    return mxfp4_linear_q(xq, sx, w)
+
+
+def mxfp4_linear_ref(xq: torch.Tensor, sx: torch.Tensor, w: Mxfp4Weight) -> torch.Tensor:
+    """fp64 [M, N] product of the activation codes, the dequantised weight and sx."""
+    x = xq.reshape(-1, w.K).double()
+    return x @ w.dequant().double().t() * sx.reshape(-1, 1).double()
+
+
+def mxfp4_as_fp8(w: Mxfp4Weight) -> Fp8Weight:
+    """The Fp8Weight that holds exactly deq(w): code * 2^E is an e4m3 value times
+    the row scale 2^(Emax - 6) while the block exponents of a row (blocks of
+    zeros aside) span at most 15 binades: 6 * 2^6 = 384 is the largest e4m3
+    value needed and 0.5 * 2^-8 the subnormal step.  ValueError otherwise."""
+    c, e = w.codes, w.scales.to(torch.int32) - 127
+    live = ((c.view(w.N, -1, MXFP4_BLOCK // 2) & 0x77) != 0).any(-1)  # blocks with a non-zero code
+    hi = torch.where(live, e, torch.full_like(e, -1000)).amax(-1)
+    lo = torch.where(live, e, torch.full_like(e, 1000)).amin(-1)
+    hi, lo = torch.where(hi < -500, torch.zeros_like(hi), hi), torch.where(lo > 500, torch.zeros_like(lo), lo)
+    bad = ((hi - lo > 14) | (hi - 6 < -126)).nonzero().flatten()
+    if bad.numel():
+        n = int(bad[0])
+        raise ValueError(f"mxfp4_as_fp8: the block exponents of row {n} span {int(hi[n] - lo[n]) + 1} binades "
+                         f"([{int(lo[n])}, {int(hi[n])}]); an e4m3 row with one power-of-two scale holds 15")
+    s = ((hi - 6 + 127) << 23).to(torch.int32).view(torch.float32)
+    inv = ((127 - (hi - 6)) << 23).to(torch.int32).view(torch.float32)
+    d = w.dequant()
+    q = (d * inv.unsqueeze(1)).to(torch.float8_e4m3fn)
+    if not torch.equal(q.float() * s.unsqueeze(1), d):
+        raise ValueError("mxfp4_as_fp8: the e4m3 copy is not exact")
+    return Fp8Weight.from_quantised(q, s)
+
+
+def linear_q(xq: torch.Tensor, sx: torch.Tensor, w, resid: Optional[torch.Tensor] = None,
+             tiled: bool = False) -> torch.Tensor:
+    """The decoder's linear on quantised rows, by the weight's type: fp8_linear_q
+    with these arguments for an Fp8Weight, mxfp4_linear_q for an Mxfp4Weight
+    (which has no tiled form)."""
+    if isinstance(w, Mxfp4Weight):
+        if tiled:
+            raise ValueError("linear_q: there is no tiled fp4 GEMM")
+        return mxfp4_linear_q(xq, sx, w, resid=resid)
+    return fp8_linear_q(xq, sx, w, resid=resid, tiled=tiled)
+
+
 # --------------------------------------------------------------------------- token sampling (csrc/hip/sample_kernels.hip)
 # Temperature, top-k and top-p sampling of one token per row, defined in integers so that the kernel and the torch
 # reference agree on every token bit for bit.  One row x[V] (bf16 or fp32; -inf allowed, NaN / +inf / an all -inf row
