@@ -191,10 +191,11 @@ class Block(nn.Module):
             mx = llm.Mxfp4Weight(w)
             self._fp8[name] = llm.mxfp4_as_fp8(mx) if emulate else mx
 
-    def forward_fp8(self, x, cos, sin, cache, pos: int, tiled: bool = False, view=None):
+    def forward_fp8(self, x, cos, sin, cache, pos: int, tiled: bool = False, view=None, tiled4: bool = False):
         """Decode/prefill block on fp8 weights (fp8 MFMA linears + fused gfx950
         RMSNorm/RoPE/SwiGLU); inference only.  ``tiled``: the linears run the
         LDS-tiled fp8 GEMM (one launch for any M) where their N allows it.
+        ``tiled4``: the same for MXFP4 weights and the tiled fp4 GEMM.
         ``view``: this layer's cache view (ops.llm: DenseUniform, DenseSeq,
         Paged, ...); the attention block is then two gfx950 launches, write and
         attend, in the view's form, and ``cache`` / ``pos`` are not used.
@@ -204,7 +205,8 @@ class Block(nn.Module):
         from ..ops import llm
         cfg, hd, f = self.cfg, self.cfg.head_dim, self._fp8
         B, S, _ = x.shape
-        qkv = llm.linear_q(*llm.rmsnorm_quant_fp8(x, self.attn_norm.weight, self.attn_norm.eps), f["qkv"], tiled=tiled)
+        qkv = llm.linear_q(*llm.rmsnorm_quant_fp8(x, self.attn_norm.weight, self.attn_norm.eps), f["qkv"], tiled=tiled,
+                           tiled4=tiled4)
         nq, nkv = cfg.n_heads * hd, cfg.n_kv_heads * hd
         if view is not None:
             o = llm.attend_prefill(view, llm.write_prefill(view, qkv, cos, sin, cfg.n_heads))
@@ -219,9 +221,10 @@ class Block(nn.Module):
             o = F.scaled_dot_product_attention(q.transpose(1, 2), kc[:, :, :pos + S], vc[:, :, :pos + S],
                                                is_causal=(S > 1), enable_gqa=True)
             o = o.transpose(1, 2).reshape(B, S, nq)
-        x = x + llm.linear_q(*llm.quant_rows_fp8(o), f["o"], tiled=tiled)
-        gu = llm.linear_q(*llm.rmsnorm_quant_fp8(x, self.mlp_norm.weight, self.mlp_norm.eps), f["w13"], tiled=tiled)
-        return x + llm.linear_q(*llm.swiglu_quant_fp8(gu), f["w2"], tiled=tiled)
+        x = x + llm.linear_q(*llm.quant_rows_fp8(o), f["o"], tiled=tiled, tiled4=tiled4)
+        gu = llm.linear_q(*llm.rmsnorm_quant_fp8(x, self.mlp_norm.weight, self.mlp_norm.eps), f["w13"], tiled=tiled,
+                          tiled4=tiled4)
+        return x + llm.linear_q(*llm.swiglu_quant_fp8(gu), f["w2"], tiled=tiled, tiled4=tiled4)
 
     def decode_fp8_static(self, x, cos, sin, cache, pos_i32, pos_i64, mask, view=None):
         """One-token decode with every shape static and the position on device
@@ -318,8 +321,10 @@ class Llama(nn.Module):
         return self
 
     def forward_fp8(self, tokens, cache, pos: int = 0, last_only: bool = False, tiled: bool = False,
-                    prefill_attn: bool = False, head: bool = True, last_idx=None, views=None):
-        """``head=False`` (a non-final chunk of a chunked prefill): fill the
+                    prefill_attn: bool = False, head: bool = True, last_idx=None, views=None, tiled4: bool = False):
+        """``tiled4``: the block linears over MXFP4 weights run the tiled fp4 GEMM
+        (Block.forward_fp8); the LM head is an Fp8Weight and follows ``tiled``.
+        ``head=False`` (a non-final chunk of a chunked prefill): fill the
         caches only, no final norm / LM head; returns None.  ``last_idx`` (long
         [B]): the head runs on token last_idx[b] of sequence b and the result is
         [B, 1, vocab].  ``views``: one cache view per layer, see
@@ -331,7 +336,8 @@ class Llama(nn.Module):
         if views is None and prefill_attn and tokens.shape[1] > 1:
             views = [llm.DenseUniform(kc, vc, pos) for kc, vc in cache]
         for i, layer in enumerate(self.layers):
-            x = layer.forward_fp8(x, cos, sin, cache[i], pos, tiled=tiled, view=None if views is None else views[i])
+            x = layer.forward_fp8(x, cos, sin, cache[i], pos, tiled=tiled, view=None if views is None else views[i],
+                                  tiled4=tiled4)
         if not head:
             return None
         if last_idx is not None:
@@ -419,7 +425,7 @@ class LlamaDecoder:
                  fused: Optional[bool] = None, fp8: bool = False, graph: bool = False, static: bool = False,
                  prefill_tiled: bool = False, prefill_attn: bool = False, ragged: bool = False,
                  paged: bool = False, pages: Optional[int] = None, page: int = 64, kv_fp8=False,
-                 sampling: bool = False, w4=False):
+                 sampling: bool = False, w4=False, w4_tiled: bool = False):
         # opt-in (needs fp8=True): the four block linears of every layer stream MXFP4 weights (ops.llm.Mxfp4Weight:
         # e2m1 codes and one E8M0 scale per 32 k, 4.25 bits per weight where fp8 stores 8) through the fp4 MFMA
         # linear; the LM head stays fp8.  Every mode on top (prefill, chunks, ragged, paged, kv_fp8, sampling, admit,
@@ -430,8 +436,15 @@ class LlamaDecoder:
         if w4 and not fp8:
             raise ValueError("LlamaDecoder: w4 runs on the fp8 path (needs fp8=True)")
         if w4 is True and prefill_tiled:
-            raise ValueError("LlamaDecoder: w4=True with prefill_tiled=True: there is no tiled fp4 GEMM")
+            raise ValueError("LlamaDecoder: w4=True with prefill_tiled=True: there is no tiled fp4 GEMM under that "
+                             "flag (w4_tiled=True selects it)")
         self.w4 = w4
+        # opt-in (needs w4=True): every forward_fp8 call (prefill, chunks, ragged, paged, kv_fp8, admit) runs its
+        # block linears as one launch of the LDS-tiled fp4 GEMM each instead of one weight-streaming launch per 64
+        # rows; the static step and its graph keep the skinny kernel and the fused residual, the LM head stays fp8
+        if w4_tiled and w4 is not True:
+            raise ValueError(f"LlamaDecoder: w4_tiled=True runs the tiled fp4 GEMM (needs w4=True, got w4={w4!r})")
+        self.w4_tiled = bool(w4_tiled)
         # opt-in (implies ragged): the KV cache is a pool of `pages` pages of
         # `page` rows per layer, [pages, Hkv, page, hd], and one block table
         # [batch, ceil(context / page)] for all layers maps every slot's logical
@@ -612,7 +625,8 @@ class LlamaDecoder:
         if self.fp8:
             return self.model.forward_fp8(tokens, cache, pos, last_only=True, tiled=self.prefill_tiled,
                                           prefill_attn=self.prefill_attn, head=head, last_idx=last_idx,
-                                          views=None if seq is None else self._views(tokens.device, *seq))
+                                          views=None if seq is None else self._views(tokens.device, *seq),
+                                          tiled4=self.w4_tiled)
         return self.model(tokens, cache=cache, pos=pos, fused=self.fused, last_only=True,
                           prefill_attn=self.prefill_attn, head=head, seq=seq, last_idx=last_idx)
 
@@ -757,7 +771,7 @@ class LlamaDecoder:
             self._sync_table()
             views = self._views(dev, pos, lens, self._table if slot is None else self._table[slot:slot + 1])
             return self.model.forward_fp8(tokens, self.cache, 0, last_only=True, tiled=self.prefill_tiled, head=head,
-                                          last_idx=last_idx, views=views)
+                                          last_idx=last_idx, views=views, tiled4=self.w4_tiled)
         dense = self._dense_rows(slots, [max(p, 0) for p in pos])
         if slot is None:
             logits = self.model(tokens, cache=dense, last_only=True, head=head, seq=(list(pos), list(lens)),
@@ -1034,7 +1048,7 @@ class LlamaDecoder:
             self.pos += 1
             return out
         if self.fp8:
-            logits = self.model.forward_fp8(tok, self.cache, self.pos)
+            logits = self.model.forward_fp8(tok, self.cache, self.pos, tiled4=self.w4_tiled)
         else:
             logits = self.model(tok, cache=self.cache, pos=self.pos, fused=self.fused)
         self.pos += 1

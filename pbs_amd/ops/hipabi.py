@@ -44,6 +44,9 @@ def bind(lib):
     _p(lib, "gpbs_hip_gemm_fp8", C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_uint,
        C.c_uint, vp, vp, C.c_int, vp)
     _p(lib, "gpbs_hip_gemm_fp8_units", C.c_int, C.c_int, C.c_int)
+    # the tiled GEMM over an MXFP4 weight: codes and E8M0 block scales in place of Bq and sb
+    _p(lib, "gpbs_hip_gemm_mxfp4", C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_uint, C.c_uint,
+       vp, vp, C.c_int, vp)
     _p(lib, "gpbs_hip_stream_copy", C.c_int, vp, vp, C.c_ulonglong, C.c_uint, vp, vp, C.c_uint, C.c_uint, vp, vp,
        C.c_int, vp)
     _p(lib, "gpbs_hip_reduce_bf16", C.c_int, vp, vp, vp, C.c_ulonglong, C.c_uint, vp, vp, C.c_uint, C.c_uint, vp, vp,

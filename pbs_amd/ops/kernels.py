@@ -109,6 +109,45 @@ def gemm_fp8(Aq: torch.Tensor, sa: torch.Tensor, Bq: torch.Tensor, sb: torch.Ten
     return out
 
 
+def gemm_mxfp4(xq: torch.Tensor, sx: torch.Tensor, w, out: Optional[torch.Tensor] = None, *, table=None,
+               tenant: int = 0, counters=None, grid: int = 0, stream=None) -> torch.Tensor:
+    """Y[M, N] (bf16) = (xq @ deq(w)^T) * sx[m] on the block-scaled MFMA with an
+    fp4 B operand (k_gemm_mxfp4_tn): xq [M, K] e4m3fn, sx [M] fp32, ``w`` an
+    ``llm.Mxfp4Weight`` as stored (``qs``, ``ss``), fp32 accumulation.  Any
+    M > 0; N % 128 == 0 and K % 256 == 0.  The library takes raw pointers, so
+    everything it reads is checked here first."""
+    if xq.dtype != torch.float8_e4m3fn or sx.dtype != torch.float32:
+        raise ValueError(f"gemm_mxfp4 needs e4m3fn rows and fp32 row scales, got {xq.dtype} {sx.dtype}")
+    if xq.dim() != 2:
+        raise ValueError(f"gemm_mxfp4 needs 2-D rows, got {tuple(xq.shape)}")
+    M, K = xq.shape
+    Nn = w.N
+    if K != w.K or M <= 0 or Nn <= 0 or Nn % 128 or K <= 0 or K % 256:
+        raise ValueError(f"gemm_mxfp4 needs N % 128 == 0 and K % 256 == 0, got {tuple(xq.shape)} x [{Nn}, {w.K}]")
+    if sx.numel() != M:
+        raise ValueError(f"gemm_mxfp4: row scales {tuple(sx.shape)} for [{M}, {Nn}]")
+    if w.qs.dtype != torch.uint8 or w.qs.numel() != Nn * K // 2 or not w.qs.is_contiguous() \
+            or w.ss.dtype != torch.uint8 or w.ss.numel() != Nn * K // 32 or not w.ss.is_contiguous():
+        raise ValueError(f"gemm_mxfp4: weight [{Nn}, {K}] with codes {w.qs.dtype} {tuple(w.qs.shape)}, scales "
+                         f"{w.ss.dtype} {tuple(w.ss.shape)}")
+    if not (xq.is_cuda and sx.is_cuda and w.qs.is_cuda and w.ss.is_cuda):
+        raise ValueError("gemm_mxfp4 needs CUDA tensors")
+    if not (sx.device == w.qs.device == w.ss.device == xq.device):
+        raise ValueError(f"gemm_mxfp4: operands on {xq.device}, {sx.device}, {w.qs.device}, {w.ss.device}")
+    xq, sx = xq.contiguous(), sx.contiguous()
+    if out is None:
+        out = torch.empty(M, Nn, dtype=torch.bfloat16, device=xq.device)
+    elif out.dtype != torch.bfloat16 or out.shape != (M, Nn) or not out.is_contiguous() or not out.is_cuda \
+            or out.device != xq.device:
+        raise ValueError(f"gemm_mxfp4: out must be a contiguous bf16 CUDA [{M}, {Nn}], got {out.dtype} "
+                         f"{tuple(out.shape)}")
+    q = work_queue(xq.device)
+    rc = lib().gpbs_hip_gemm_mxfp4(_ptr(xq), _ptr(sx), _ptr(w.qs), _ptr(w.ss), _ptr(out), M, Nn, K, _ptr(q), table,
+                                   GATE_TABLE if table else GATE_NONE, tenant, counters, None, grid, _stream(stream))
+    _check(rc, "gemm_mxfp4")
+    return out
+
+
 def stream_copy(src: torch.Tensor, dst: torch.Tensor, *, chunk_bytes: int = 1 << 19, table=None, tenant: int = 0,
                 counters=None, grid: int = 0, stream=None, mode_extra: int = 0):
     """``mode_extra``: gate-mode bits OR-ed in when ``table`` is given

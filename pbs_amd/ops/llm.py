@@ -12,7 +12,7 @@ from typing import Optional
 
 import torch
 
-from .kernels import _check, _ptr, _stream, gemm_fp8, lib
+from .kernels import _check, _ptr, _stream, gemm_fp8, gemm_mxfp4, lib
 
 
 def _need(t: torch.Tensor, what: str):
@@ -1024,11 +1024,13 @@ def mxfp4_scale_offset(n: int, k: int, K: int) -> int:
 
 
 def mxfp4_linear_q(xq: torch.Tensor, sx: torch.Tensor, w: Mxfp4Weight,
-                   resid: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   resid: Optional[torch.Tensor] = None, tiled: bool = False) -> torch.Tensor:
     """y = (xq @ deq(W)^T) * sx[m] (+ resid, fused into the epilogue) on
     already-quantised e4m3 rows, as fp8_linear_q; bf16 out.  M > 64 without a
-    residual runs one launch per 64 rows.  The library takes raw pointers, so
-    everything it reads is checked here first."""
+    residual runs one launch per 64 rows.  ``tiled`` (opt-in, no resid,
+    N % 128 == 0): one launch of the LDS-tiled fp4 GEMM (gemm_mxfp4) for any M
+    instead.  The library takes raw pointers, so everything it reads is checked
+    here first."""
     lead = xq.shape[:-1]
     if xq.dtype != torch.float8_e4m3fn or xq.shape[-1] != w.K or not xq.is_contiguous():
         raise ValueError(f"mxfp4_linear_q: need contiguous e4m3fn [..., {w.K}], got {xq.dtype} {tuple(xq.shape)}")
@@ -1054,6 +1056,9 @@ def mxfp4_linear_q(xq: torch.Tensor, sx: torch.Tensor, w: Mxfp4Weight,
     if resid is not None and M > FP8_M_TILE:
         raise ValueError(f"mxfp4_linear_q: resid {tuple(resid.shape)} for [{M}, {w.N}] (M <= {FP8_M_TILE})")
     y = torch.empty(*lead, w.N, dtype=torch.bfloat16, device=xq.device)
+    if tiled and resid is None and w.N % 128 == 0:
+        gemm_mxfp4(xq.view(M, w.K), sx.reshape(M), w, y.view(M, w.N))
+        return y
     L, st = lib(), _stream()
     if resid is not None:
         _check(L.gpbs_hip_mxfp4_linear_res(_ptr(xq), _ptr(sx), _ptr(w.qs), _ptr(w.ss), _ptr(y), _ptr(resid), M, w.N,
@@ -1071,10 +1076,11 @@ def mxfp4_linear_q(xq: torch.Tensor, sx: torch.Tensor, w: Mxfp4Weight,
     return y
 
 
-def mxfp4_linear(x: torch.Tensor, w: Mxfp4Weight) -> torch.Tensor:
-    """y = x @ deq(W)^T with x [..., K] bf16 quantised per token to fp8 on the fly."""
+def mxfp4_linear(x: torch.Tensor, w: Mxfp4Weight, tiled: bool = False) -> torch.Tensor:
+    """y = x @ deq(W)^T with x [..., K] bf16 quantised per token to fp8 on the
+    fly.  ``tiled``: as mxfp4_linear_q."""
     xq, sx = quant_rows_fp8(x)
-    return mxfp4_linear_q(xq, sx, w)
+    return mxfp4_linear_q(xq, sx, w, tiled=tiled)
 
 
 def mxfp4_linear_ref(xq: torch.Tensor, sx: torch.Tensor, w: Mxfp4Weight) -> torch.Tensor:
@@ -1108,14 +1114,16 @@ def mxfp4_as_fp8(w: Mxfp4Weight) -> Fp8Weight:
 
 
 def linear_q(xq: torch.Tensor, sx: torch.Tensor, w, resid: Optional[torch.Tensor] = None,
-             tiled: bool = False) -> torch.Tensor:
+             tiled: bool = False, tiled4: bool = False) -> torch.Tensor:
     """The decoder's linear on quantised rows, by the weight's type: fp8_linear_q
-    with these arguments for an Fp8Weight, mxfp4_linear_q for an Mxfp4Weight
-    (which has no tiled form)."""
+    with ``tiled`` for an Fp8Weight, mxfp4_linear_q with ``tiled4`` as its
+    ``tiled`` for an Mxfp4Weight.  The two flags are separate: ``tiled`` with an
+    Mxfp4Weight stays an error (it asks for the fp8 GEMM, which cannot read fp4
+    codes), and ``tiled4`` is ignored for an Fp8Weight."""
     if isinstance(w, Mxfp4Weight):
         if tiled:
-            raise ValueError("linear_q: there is no tiled fp4 GEMM")
-        return mxfp4_linear_q(xq, sx, w, resid=resid)
+            raise ValueError("linear_q: there is no tiled fp4 GEMM under tiled=True (tiled4=True selects it)")
+        return mxfp4_linear_q(xq, sx, w, resid=resid, tiled=tiled4)
     return fp8_linear_q(xq, sx, w, resid=resid, tiled=tiled)
 
 
