@@ -12,20 +12,16 @@
 // the lane's scale register.  Accumulation is fp32, the output one RNE
 // rounding to bf16; there is no residual form.
 //
-// Structure of k_gemm_fp8_tn (fp8_gemm_kernels.hip): persistent workgroups
-// over the tile queue, ownership re-checked between tiles, 128x128 output
-// tile, 4 waves (2x2) of 64x64, each a 4x4 grid of 16x16 blocks, GROUP_M = 8,
-// operands staged by global_load_lds_dwordx4 in 1 KiB pieces, two buffers of
-// 128 k.  What differs:
+// The tile loop, the A image and its staging, and the epilogue walk are
+// gemm_q_tile.hpp's, shared with k_gemm_fp8_tn (fp8_gemm_kernels.hip).  What
+// is this kernel's:
 //
-// A operand.  The image is that kernel's: [128 rows][128 B], 16-B chunk c of
-// row r at slot c ^ (r & 7).  The fragment is not.  Against an fp4 B the
-// instruction's own k map of the e4m3 operand decides which products are
-// formed: for lane group g = lane >> 4, VGPRs 0..3 are k = 16 g .. + 16 and
-// VGPRs 4..7 are k = 64 + 16 g .. + 16 of the 128-k step (measured in
-// fp4_kernels.hip).  So the lane of row r reads chunks g and 4 + g, at slots
-// g ^ (r & 7) and (4 + g) ^ (r & 7); the fp8 kernel's 2 g, 2 g + 1 would pair
-// every k with the wrong weight.
+// A fragment.  Against an fp4 B the instruction's own k map of the e4m3
+// operand decides which products are formed: for lane group g = lane >> 4,
+// VGPRs 0..3 are k = 16 g .. + 16 and VGPRs 4..7 are k = 64 + 16 g .. + 16 of
+// the 128-k step (measured in fp4_kernels.hip).  So the lane of row r reads
+// chunks g and 4 + g, at slots g ^ (r & 7) and (4 + g) ^ (r & 7); the fp8
+// kernel's 2 g, 2 g + 1 would pair every k with the wrong weight.
 //
 // B operand.  The codes of a 16-row strip for one 128-k step (block kb of 256
 // k, step u) are one contiguous 1 KiB run of qs, at ((n / 16) (K / 256) + kb)
@@ -46,119 +42,49 @@
 // 1 on buffer 1 (K % 256 == 0 makes the count of 128-k steps even).
 //
 // LDS: 2 x (16 + 8) KiB + 1 KiB of scales + the queue slot: two workgroups
-// per CU.  Ragged M: any M > 0, the staged row is clamped to M - 1 and rows >=
-// M are not stored.  N % 128 == 0 and K % 256 == 0.
-#include "common.hpp"
+// per CU.  N % 128 == 0 and K % 256 == 0.
+#include "gemm_q_tile.hpp"
 
 namespace gpbs_fp4g {
 
-using namespace gpbs_hip;
+using namespace gpbs_qtile;
 
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) char lds_t;
-
-constexpr int QBM = 128, QBN = 128, QBK = 128, QNT = 256;
-constexpr int kTileA = QBM * QBK;        // bytes of the e4m3 A image of one step
-constexpr int kTileB = QBN * QBK / 2;    // bytes of the fp4 B image of one step: 8 strips of 1 KiB
+constexpr int kTileB = BN * BK / 2;      // bytes of the fp4 B image of one step: 8 strips of 1 KiB
 constexpr int kBuf = kTileA + kTileB;    // one buffer: [A | B]
-constexpr int kScale = (QBN / 16) * 128; // scale words of one 256-k block: [8 strips][64 lanes][2 B]
-constexpr int kLds = 2 * kBuf + kScale;
-constexpr int kOne = 0x7f7f7f7f;         // E8M0 1.0 in every byte: the scale of the e4m3 operand
+constexpr int kScale = (BN / 16) * 128;  // scale words of one 256-k block: [8 strips][64 lanes][2 B]
 
-__device__ __forceinline__ void glds16(const void* g, lds_t* l) {
-  __builtin_amdgcn_global_load_lds(g, (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
+struct None {};  // what col(n) loads here: the output has no per-column factor
 
-// The rounding of k_mxfp4_gemm_skinny, so both kernels give the same bits on
-// the same fp32 value.
-__device__ __forceinline__ u16 f2bf(float f) {
-  u32 u = __float_as_uint(f);
-  u += 0x7fffu + ((u >> 16) & 1u);  // round to nearest even
-  return (u16)(u >> 16);
-}
+struct Mxfp4Tile {
+  static constexpr int kLds = 2 * kBuf + kScale;
+  const unsigned char* __restrict__ Bq;
+  const unsigned char* __restrict__ Bs;
 
-__global__ __launch_bounds__(QNT, 2) void k_gemm_mxfp4_tn(const unsigned char* __restrict__ A,
-                                                          const float* __restrict__ sa,
-                                                          const unsigned char* __restrict__ Bq,
-                                                          const unsigned char* __restrict__ Bs, u16* __restrict__ C,
-                                                          int M, int N, int K, WorkQueue* q, const PartTable* table,
-                                                          u32 mode, u32 me, u64* cnt, u32 inst_per_tile,
-                                                          u32 refs_per_tile, u32 miss_per_tile, u32* status) {
-  __shared__ __attribute__((aligned(16))) char smem[kLds + 16];
-  lds_t* lds = (lds_t*)smem;
-  lds_t* lsc = lds + 2 * kBuf;
-  int* s_slot = (int*)(smem + kLds);
-  const u32 xcc = xcc_id();
-  u64 t_last = __builtin_amdgcn_s_memtime();
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int wr = wid >> 1, wc = wid & 1;
-  const int tiles_m = (M + QBM - 1) / QBM, tiles_n = N / QBN, ntiles = tiles_m * tiles_n;
-  const int nkb = K >> 8;  // blocks of 256 k = two 128-k steps
-  constexpr int GROUP_M = 8;
-
-  // A staging geometry of k_gemm_fp8_tn: this wave loads pieces c = wid*4 + j
-  // (8 rows of 128 B each); lane -> row 8c + lane/8, LDS slot lane%8, global
-  // 16-B chunk (slot ^ (row & 7)) of the K-tile.
-  int srow[4], schunk[4];
+  __device__ __forceinline__ void k_loop(const Lanes& L, lds_t* lds, const unsigned char* __restrict__ A,
+                                         const size_t (&aoff)[4], int tn, int K, f32x4 (&acc)[4][4]) const {
+    const int nkb = K >> 8;  // blocks of 256 k = two 128-k steps
+    const int wid = L.wid, lane = L.lane, wr = L.wr, wc = L.wc;
+    lds_t* lsc = lds + 2 * kBuf;
+    // Source byte offsets at step 0: the two B strips 2 wid and 2 wid + 1 (one
+    // 1 KiB run per step, 1 KiB on per step: u = 1 follows u = 0 and the next
+    // block follows that), and this lane's 16 bytes of the tile's scale words
+    // (128 B on per block).
+    size_t boff[2];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    srow[j] = 8 * (wid * 4 + j) + (lane >> 3);
-    schunk[j] = (lane & 7) ^ (srow[j] & 7);
-  }
-  const int l16 = lane & 15, lq = lane >> 4;
-
-  for (;;) {
-    const int t = grab_unit(q, table, mode, me, xcc, s_slot, (u32)ntiles);
-    if (t < 0) break;
-    // L2-friendly grouped order (GROUP_M row panels share B column panels).
-    const int in_group = GROUP_M * tiles_n;
-    const int g = t / in_group;
-    const int first_m = g * GROUP_M;
-    const int gsz = min(tiles_m - first_m, GROUP_M);
-    const int tm = first_m + (t % in_group) % gsz;
-    const int tn = (t % in_group) / gsz;
-
-    // Source byte offsets at step 0: four A pieces, the two B strips 2 wid and
-    // 2 wid + 1 (one 1 KiB run per step, 1 KiB on per step: u = 1 follows u = 0
-    // and the next block follows that), and this lane's 16 bytes of the tile's
-    // scale words (128 B on per block).
-    size_t aoff[4], boff[2];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int ra = min(tm * QBM + srow[j], M - 1);  // ragged M: clamp, never read past the last row
-      aoff[j] = (size_t)ra * K + schunk[j] * 16;
-    }
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-      boff[j] = (size_t)(tn * (QBN / 16) + wid * 2 + j) * nkb * 2048 + lane * 16;
-    const size_t soff = (size_t)(tn * (QBN / 16) + (lane >> 3)) * nkb * 128 + (lane & 7) * 16;
-
-    f32x4 acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
+    for (int j = 0; j < 2; ++j) boff[j] = (size_t)(tn * (BN / 16) + wid * 2 + j) * nkb * 2048 + lane * 16;
+    const size_t soff = (size_t)(tn * (BN / 16) + (lane >> 3)) * nkb * 128 + (lane & 7) * 16;
     // Step kt (128 k) into buffer buf; the first step of a block brings the
     // block's scale words with it (wave 0, one instruction).
     auto stage = [&](int buf, int kt, bool scales) {
       lds_t* la = lds + buf * kBuf;
       lds_t* lb = la + kTileA;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) glds16(A + aoff[j] + (size_t)kt * QBK, la + (wid * 4 + j) * 1024);
+      L.stage_a(A, aoff, kt, la);
 #pragma unroll
       for (int j = 0; j < 2; ++j) glds16(Bq + boff[j] + (size_t)kt * 1024, lb + (wid * 2 + j) * 1024);
       if (scales && wid == 0) glds16(Bs + soff + (size_t)(kt >> 1) * 128, lsc);
     };
-    // 16 rows from r0 of the A image: the lane of row r0 + l16 reads the k the
-    // instruction takes from it, chunks lq and 4 + lq.
-    auto frag_a = [&](const lds_t* img, int r0) -> i32x8 {
-      const int r = r0 + l16;
-      const lds_t* row = img + r * 128;
-      const u32x4 lo = *(const __attribute__((address_space(3))) u32x4*)(row + ((lq ^ (r & 7)) << 4));
-      const u32x4 hi = *(const __attribute__((address_space(3))) u32x4*)(row + (((4 + lq) ^ (r & 7)) << 4));
-      return i32x8{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
-    };
+    // 16 rows from r0 of the A image: the k the instruction takes from the lane of row r0 + l16.
+    auto frag_a = [&](const lds_t* img, int r0) -> i32x8 { return L.frag_rows(img, r0, L.lq, 4 + L.lq); };
     // The lane's 32 codes of one strip: the first 4 of the 8 registers.
     auto frag_b = [&](const lds_t* img, int strip) -> i32x8 {
       const u32x4 v = *(const __attribute__((address_space(3))) u32x4*)(img + strip * 1024 + lane * 16);
@@ -210,21 +136,27 @@ __global__ __launch_bounds__(QNT, 2) void k_gemm_mxfp4_tn(const unsigned char* _
         __syncthreads();
       }
     }
-    // Epilogue: D(row = (lane>>4)*4 + r, col = lane&15) per 16x16 block.
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int n = tn * QBN + wc * 64 + j * 16 + l16;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int m = tm * QBM + wr * 64 + i * 16 + lq * 4;
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          if (m + r < M) C[(size_t)(m + r) * N + n] = f2bf(acc[i][j][r] * sa[m + r]);
-      }
-    }
-    count_unit(cnt, me, xcc, inst_per_tile, &t_last, refs_per_tile, miss_per_tile, q);
   }
-  finish(q, status, (u32)ntiles);
+
+  // No column factor.  The rounding is that of k_mxfp4_gemm_skinny, so both
+  // kernels give the same bits on the same fp32 value.
+  __device__ __forceinline__ None col(int) const { return {}; }
+  static __device__ __forceinline__ u16 out(float acc, float sa, None) {
+    u32 u = __float_as_uint(acc * sa);
+    u += 0x7fffu + ((u >> 16) & 1u);  // round to nearest even
+    return (u16)(u >> 16);
+  }
+};
+
+__global__ __launch_bounds__(NT, 2) void k_gemm_mxfp4_tn(const unsigned char* __restrict__ A,
+                                                         const float* __restrict__ sa,
+                                                         const unsigned char* __restrict__ Bq,
+                                                         const unsigned char* __restrict__ Bs, u16* __restrict__ C,
+                                                         int M, int N, int K, WorkQueue* q, const PartTable* table,
+                                                         u32 mode, u32 me, u64* cnt, u32 inst_per_tile,
+                                                         u32 refs_per_tile, u32 miss_per_tile, u32* status) {
+  tile_loop(Mxfp4Tile{Bq, Bs}, A, sa, C, M, N, K, q, table, mode, me, cnt, inst_per_tile, refs_per_tile,
+            miss_per_tile, status);
 }
 
 }  // namespace gpbs_fp4g
@@ -236,20 +168,19 @@ extern "C" {
 int gpbs_hip_gemm_mxfp4(const void* xq, const float* sx, const void* wq, const void* ws, void* y, int M, int N, int K,
                         void* q, const void* table, unsigned mode, unsigned me, void* cnt, void* status, int grid,
                         hipStream_t s) {
-  if (M <= 0 || N <= 0 || K <= 0 || N % QBN || K % 256) return -22;
-  const int ntiles = ((M + QBM - 1) / QBM) * (N / QBN);
-  if (grid <= 0) grid = 256 * 2;
-  if (grid > ntiles) grid = ntiles;
+  if (M <= 0 || N <= 0 || K <= 0 || N % BN || K % 256) return -22;
+  const int ntiles = tile_count(M, N);
+  grid = launch_grid(grid, ntiles);
   // The model of gpbs_hip_gemm_fp8 with this kernel's counts.  Per tile and
   // 256-k block (4 waves): 128 MFMA, 32 A + 16 B + 1 scale glds, 64 A + 32 B
   // ds_read_b128 and 16 scale reads.  refs = the A panel, the B panel at half
   // a byte per element and its scale bytes (one per 32 k) in 128-B lines;
   // fills = the compulsory bytes spread over the tiles + the C tile.
   const u32 inst = (u32)((K / 256) * (128 + 49 + 96 + 16) + 64);
-  const u32 refs = (u32)(((u64)QBM * K + (u64)QBN * K / 2 + (u64)QBN * K / 32) / 128);
+  const u32 refs = (u32)(((u64)BM * K + (u64)BN * K / 2 + (u64)BN * K / 32) / 128);
   const u32 miss =
-      (u32)((((u64)M * K + (u64)N * K / 2 + (u64)N * K / 32) / 128) / ntiles + (u64)QBM * QBN * 2 / 128);
-  hipLaunchKernelGGL(k_gemm_mxfp4_tn, dim3(grid), dim3(QNT), 0, s, (const unsigned char*)xq, sx,
+      (u32)((((u64)M * K + (u64)N * K / 2 + (u64)N * K / 32) / 128) / ntiles + (u64)BM * BN * 2 / 128);
+  hipLaunchKernelGGL(k_gemm_mxfp4_tn, dim3(grid), dim3(NT), 0, s, (const unsigned char*)xq, sx,
                      (const unsigned char*)wq, (const unsigned char*)ws, (u16*)y, M, N, K, (WorkQueue*)q,
                      (const PartTable*)table, mode, me, (u64*)cnt, inst, refs, miss, (u32*)status);
   return hipGetLastError() == hipSuccess ? 0 : -5;

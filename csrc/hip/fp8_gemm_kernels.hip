@@ -13,28 +13,18 @@
 // scales are all 1.0 (0x7f in every byte, so the op_sel byte choice cannot
 // matter); the real scales are applied in the epilogue.
 //
-// Structure of k_gemm_bf16_tn (tenant_kernels.hip): persistent workgroups
-// over a tile queue, ownership re-checked between tiles, 128x128 output
-// tile, 4 waves (2x2) of 64x64, each a 4x4 grid of 16x16 blocks.  BK = 128
-// e4m3 elements = one 128-byte row, so the staging geometry is that
-// kernel's byte for byte: [buf][A|B][128 rows][128 B] (64 KiB, 2 workgroups
-// per CU), filled by global_load_lds_dwordx4 in 1 KiB pieces of 8 rows, 16-B
-// chunk c of row r kept at slot c ^ (r & 7) (the swizzle is applied on the
-// global SOURCE address, LDS is written lane-linear).  One MFMA per 16x16
-// block per K-tile: 16 per wave per K-tile.
+// The tile loop, the A staging and the epilogue walk are gemm_q_tile.hpp's.
+// Row-major B is staged as A is, byte for byte: LDS holds [buf][A|B][128
+// rows][128 B] (64 KiB, 2 workgroups per CU).
 //
 // Operand fragments: lane l holds row / column (l & 15) and the 32
-// consecutive k bytes from 32 * (l >> 4): two ds_read_b128 per fragment
-// (chunks 2g and 2g + 1, g = l >> 4).  A and B fragments are built the same
-// way, so each lane group pairs the same 32 k's of both operands and the sum
-// is right whatever k the hardware gives each byte.  The instruction's own
-// map of an e4m3 operand is not this one (fp4_kernels.hip measured it:
-// VGPRs 0..3 are k = 16 g .. + 16, VGPRs 4..7 k = 64 + 16 g .. + 16); it
-// matters only where the two operands differ in format or carry real scales.
-//
-// Ragged M: any M > 0.  Staging clamps the row index to M - 1 (the clamped
-// rows feed only accumulators whose stores are skipped), rows >= M are not
-// stored.  N % 128 == 0 and K % 128 == 0.
+// consecutive k bytes from 32 * (l >> 4): chunks 2g and 2g + 1, g = l >> 4.
+// A and B fragments are built the same way, so each lane group pairs the same
+// 32 k's of both operands and the sum is right whatever k the hardware gives
+// each byte.  The instruction's own map of an e4m3 operand is not this one
+// (fp4_kernels.hip measured it: VGPRs 0..3 are k = 16 g .. + 16, VGPRs 4..7
+// k = 64 + 16 g .. + 16); it matters only where the two operands differ in
+// format or carry real scales.
 //
 // BSHUF = 1: B is llm.Fp8Weight.qs, the lane-order layout of the skinny
 // kernel: the 16 bytes W[n][k .. k+16), k % 16 == 0, live at
@@ -54,115 +44,48 @@
 // swizzle needed).  The lane -> (row, k) map, the MFMA order and the
 // epilogue are those of BSHUF = 0, so both give the same bits on the same
 // operands.
-#include "common.hpp"
+#include "gemm_q_tile.hpp"
 
 namespace gpbs_fp8g {
 
-using namespace gpbs_hip;
-
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) char lds_t;
-
-constexpr int FBM = 128, FBN = 128, FBK = 128, FNT = 256;
-constexpr int kTile = FBM * FBK;          // bytes of one operand tile
-constexpr int kLds = 2 * 2 * kTile;       // [buf][A|B][128][128 B]
-constexpr int kOne = 0x7f7f7f7f;          // E8M0 1.0 in every byte
-
-__device__ __forceinline__ void glds16(const void* g, lds_t* l) {
-  __builtin_amdgcn_global_load_lds(g, (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
-
-__device__ __forceinline__ u16 f2bf(float x) { return __builtin_bit_cast(u16, (__bf16)x); }
+using namespace gpbs_qtile;
 
 template <int BSHUF>
-__global__ __launch_bounds__(FNT, 2) void k_gemm_fp8_tn(const unsigned char* __restrict__ A,
-                                                        const float* __restrict__ sa,
-                                                        const unsigned char* __restrict__ B,
-                                                        const float* __restrict__ sb, u16* __restrict__ C, int M,
-                                                        int N, int K, WorkQueue* q, const PartTable* table, u32 mode,
-                                                        u32 me, u64* cnt, u32 inst_per_tile, u32 refs_per_tile,
-                                                        u32 miss_per_tile, u32* status) {
-  __shared__ __attribute__((aligned(16))) char smem[kLds + 16];
-  lds_t* lds = (lds_t*)smem;
-  int* s_slot = (int*)(smem + kLds);
-  const u32 xcc = xcc_id();
-  u64 t_last = __builtin_amdgcn_s_memtime();
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int wr = wid >> 1, wc = wid & 1;
-  const int tiles_m = (M + FBM - 1) / FBM, tiles_n = N / FBN, ntiles = tiles_m * tiles_n;
-  const int nk = K / FBK;
-  constexpr int GROUP_M = 8;
+struct Fp8Tile {
+  static constexpr int kLds = 2 * 2 * kTileA;  // [buf][A|B][128][128 B]
+  const unsigned char* __restrict__ B;
+  const float* __restrict__ sb;
 
-  // Per-lane staging geometry: this wave loads pieces c = wid*4 + j (8 rows of
-  // 128 B each); lane -> row 8c + lane/8, LDS slot lane%8, global 16-B chunk
-  // (slot ^ (row & 7)) of the K-tile.
-  int srow[4], schunk[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    srow[j] = 8 * (wid * 4 + j) + (lane >> 3);
-    schunk[j] = (lane & 7) ^ (srow[j] & 7);
-  }
-  const int l16 = lane & 15, lq = lane >> 4;
-
-  for (;;) {
-    const int t = grab_unit(q, table, mode, me, xcc, s_slot, (u32)ntiles);
-    if (t < 0) break;
-    // L2-friendly grouped order (GROUP_M row panels share B column panels).
-    const int in_group = GROUP_M * tiles_n;
-    const int g = t / in_group;
-    const int first_m = g * GROUP_M;
-    const int gsz = min(tiles_m - first_m, GROUP_M);
-    const int tm = first_m + (t % in_group) % gsz;
-    const int tn = (t % in_group) / gsz;
-
-    // Source byte offsets of this lane's four pieces at K-tile 0.
-    size_t aoff[4], boff[4];
-    int bstep;  // B bytes per K-tile at fixed (row, chunk)
+  __device__ __forceinline__ void k_loop(const Lanes& L, lds_t* lds, const unsigned char* __restrict__ A,
+                                         const size_t (&aoff)[4], int tn, int K, f32x4 (&acc)[4][4]) const {
+    size_t boff[4];  // source byte offsets of this lane's four B pieces at K-tile 0
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const int ra = min(tm * FBM + srow[j], M - 1);  // ragged M: clamp, never read past the last row
-      aoff[j] = (size_t)ra * K + schunk[j] * 16;
       if (BSHUF) {
         // piece p = 4 wid + j: strip p/2 of the tile, k half p%2.  k = 128 kt +
         // 64 half + 16 chunk: block k/256 = kt/2, step u = 2 (kt & 1) + half,
         // then [chunk][row][16 B] = lane order
-        const int p = wid * 4 + j;
-        boff[j] = (size_t)(tn * (FBN / 16) + (p >> 1)) * (K >> 8) * 4096 + (p & 1) * 1024 + lane * 16;
+        const int p = L.wid * 4 + j;
+        boff[j] = (size_t)(tn * (BN / 16) + (p >> 1)) * (K >> 8) * 4096 + (p & 1) * 1024 + L.lane * 16;
       } else {
-        boff[j] = (size_t)(tn * FBN + srow[j]) * K + schunk[j] * 16;
+        boff[j] = (size_t)(tn * BN + L.srow(j)) * K + L.schunk(j) * 16;
       }
     }
-    bstep = BSHUF ? 2048 : FBK;
-
-    f32x4 acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
+    const int nk = K / BK;  // steps of 128 k on alternating buffers; K % 128 == 0, the count may be odd (BSHUF = 0)
+    constexpr int bstep = BSHUF ? 2048 : BK;  // B bytes per K-tile at fixed (row, chunk)
     auto stage = [&](int buf, int kt) {
-      lds_t* la = lds + buf * (2 * kTile);
-      lds_t* lb = la + kTile;
+      lds_t* la = lds + buf * (2 * kTileA);
+      lds_t* lb = la + kTileA;
+      L.stage_a(A, aoff, kt, la);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int c = wid * 4 + j;
-        glds16(A + aoff[j] + (size_t)kt * FBK, la + c * 1024);
-        glds16(B + boff[j] + (size_t)kt * bstep, lb + c * 1024);
-      }
+      for (int j = 0; j < 4; ++j) glds16(B + boff[j] + (size_t)kt * bstep, lb + (L.wid * 4 + j) * 1024);
     };
-    // 16 rows from r0 of an operand image, all 128 k: lane reads row r0 + l16,
-    // k bytes 32 lq .. 32 lq + 31 = logical chunks 2 lq, 2 lq + 1.
-    auto frag = [&](const lds_t* img, int r0) -> i32x8 {
-      const int r = r0 + l16;
-      const lds_t* row = img + r * 128;
-      const u32x4 lo = *(const __attribute__((address_space(3))) u32x4*)(row + (((2 * lq) ^ (r & 7)) << 4));
-      const u32x4 hi = *(const __attribute__((address_space(3))) u32x4*)(row + (((2 * lq + 1) ^ (r & 7)) << 4));
-      return i32x8{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
-    };
+    // 16 rows from r0 of a row-major image: k bytes 32 lq .. 32 lq + 31 of row r0 + l16.
+    auto frag = [&](const lds_t* img, int r0) -> i32x8 { return L.frag_rows(img, r0, 2 * L.lq, 2 * L.lq + 1); };
     // The same fragment of the BSHUF = 1 B image (r0 % 16 == 0): strip r0/16,
     // piece of k half lq/2, chunks 2 (lq & 1) and + 1 of its [chunk][row][16 B].
     auto frag_shuf = [&](const lds_t* img, int r0) -> i32x8 {
-      const lds_t* p = img + ((r0 >> 4) * 2 + (lq >> 1)) * 1024 + (lq & 1) * 512 + l16 * 16;
+      const lds_t* p = img + ((r0 >> 4) * 2 + (L.lq >> 1)) * 1024 + (L.lq & 1) * 512 + L.l16 * 16;
       const u32x4 lo = *(const __attribute__((address_space(3))) u32x4*)p;
       const u32x4 hi = *(const __attribute__((address_space(3))) u32x4*)(p + 256);
       return i32x8{(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
@@ -174,13 +97,13 @@ __global__ __launch_bounds__(FNT, 2) void k_gemm_fp8_tn(const unsigned char* __r
     int cur = 0;
     for (int kt = 0; kt < nk; ++kt) {
       if (kt + 1 < nk) stage(cur ^ 1, kt + 1);
-      const lds_t* la = lds + cur * (2 * kTile);
-      const lds_t* lb = la + kTile;
+      const lds_t* la = lds + cur * (2 * kTileA);
+      const lds_t* lb = la + kTileA;
       i32x8 a[4], b[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        a[i] = frag(la, wr * 64 + i * 16);
-        b[i] = BSHUF ? frag_shuf(lb, wc * 64 + i * 16) : frag(lb, wc * 64 + i * 16);
+        a[i] = frag(la, L.wr * 64 + i * 16);
+        b[i] = BSHUF ? frag_shuf(lb, L.wc * 64 + i * 16) : frag(lb, L.wc * 64 + i * 16);
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i)
@@ -191,22 +114,24 @@ __global__ __launch_bounds__(FNT, 2) void k_gemm_fp8_tn(const unsigned char* __r
       __syncthreads();
       cur ^= 1;
     }
-    // Epilogue: D(row = (lane>>4)*4 + r, col = lane&15) per 16x16 block.
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int n = tn * FBN + wc * 64 + j * 16 + l16;
-      const float wsc = sb[n];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int m = tm * FBM + wr * 64 + i * 16 + lq * 4;
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          if (m + r < M) C[(size_t)(m + r) * N + n] = f2bf((acc[i][j][r] * sa[m + r]) * wsc);
-      }
-    }
-    count_unit(cnt, me, xcc, inst_per_tile, &t_last, refs_per_tile, miss_per_tile, q);
   }
-  finish(q, status, (u32)ntiles);
+
+  __device__ __forceinline__ float col(int n) const { return sb[n]; }
+  static __device__ __forceinline__ u16 out(float acc, float sa, float wsc) {
+    return __builtin_bit_cast(u16, (__bf16)((acc * sa) * wsc));
+  }
+};
+
+template <int BSHUF>
+__global__ __launch_bounds__(NT, 2) void k_gemm_fp8_tn(const unsigned char* __restrict__ A,
+                                                       const float* __restrict__ sa,
+                                                       const unsigned char* __restrict__ B,
+                                                       const float* __restrict__ sb, u16* __restrict__ C, int M,
+                                                       int N, int K, WorkQueue* q, const PartTable* table, u32 mode,
+                                                       u32 me, u64* cnt, u32 inst_per_tile, u32 refs_per_tile,
+                                                       u32 miss_per_tile, u32* status) {
+  tile_loop(Fp8Tile<BSHUF>{B, sb}, A, sa, C, M, N, K, q, table, mode, me, cnt, inst_per_tile, refs_per_tile,
+            miss_per_tile, status);
 }
 
 }  // namespace gpbs_fp8g
@@ -215,26 +140,22 @@ using namespace gpbs_fp8g;
 
 extern "C" {
 
-int gpbs_hip_gemm_fp8_units(int M, int N) {
-  if (M <= 0 || N <= 0 || N % FBN) return 0;
-  return ((M + FBM - 1) / FBM) * (N / FBN);
-}
+int gpbs_hip_gemm_fp8_units(int M, int N) { return tile_count(M, N); }
 
 int gpbs_hip_gemm_fp8(const void* Aq, const float* sa, const void* Bq, const float* sb, void* C, int M, int N, int K,
                       int b_shuffled, void* q, const void* table, unsigned mode, unsigned me, void* cnt, void* status,
                       int grid, hipStream_t s) {
-  if (M <= 0 || N <= 0 || K <= 0 || N % FBN || K % FBK || (b_shuffled && K % 256)) return -22;
-  const int ntiles = ((M + FBM - 1) / FBM) * (N / FBN);
-  if (grid <= 0) grid = 256 * 2;
-  if (grid > ntiles) grid = ntiles;
+  if (M <= 0 || N <= 0 || K <= 0 || N % BN || K % BK || (b_shuffled && K % 256)) return -22;
+  const int ntiles = tile_count(M, N);
+  grid = launch_grid(grid, ntiles);
   // Model of the 128x128 bf16 path with fp8 byte counts: per tile and K-tile
   // 64 MFMA + 32 glds + 64 ds_read_b128 (4 waves); refs = A + B panels in
   // 128-B lines; fills = compulsory bytes spread over the tiles + the C tile.
-  const u32 inst = (u32)((K / FBK) * (64 + 32 + 64) + 64);
-  const u32 refs = (u32)(((u64)(FBM + FBN) * K) / 128);
-  const u32 miss = (u32)((((u64)M + N) * K / 128) / ntiles + (u64)FBM * FBN * 2 / 128);
+  const u32 inst = (u32)((K / BK) * (64 + 32 + 64) + 64);
+  const u32 refs = (u32)(((u64)(BM + BN) * K) / 128);
+  const u32 miss = (u32)((((u64)M + N) * K / 128) / ntiles + (u64)BM * BN * 2 / 128);
   auto kern = b_shuffled ? k_gemm_fp8_tn<1> : k_gemm_fp8_tn<0>;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(FNT), 0, s, (const unsigned char*)Aq, sa, (const unsigned char*)Bq, sb,
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), 0, s, (const unsigned char*)Aq, sa, (const unsigned char*)Bq, sb,
                      (u16*)C, M, N, K, (WorkQueue*)q, (const PartTable*)table, mode, me, (u64*)cnt, inst, refs, miss,
                      (u32*)status);
   return hipGetLastError() == hipSuccess ? 0 : -5;
