@@ -273,9 +273,13 @@ __global__ __launch_bounds__(GNT, 2) void k_gemm_bf16_tn(const u16* __restrict__
 //     against 1129 with 2-D blocks -- the dispatch already deals consecutive
 //     tickets round-robin over the XCDs.
 //   kGemmStatic (opts bit 23; ungated launches with one unit per workgroup
-//     only): unit = blockIdx.x, no work-queue atomic.  A diagnostic of what the
-//     persistent queue -- which gating, parking and relaunch need -- costs a
-//     solo launch (scripts/gemm_shapes.py); never set by the runners.  Measured
+//     that pass neither a status word nor a counter block only): unit =
+//     blockIdx.x, no work-queue atomic.  A diagnostic of what the persistent
+//     queue -- which gating, parking and relaunch need -- costs a solo launch
+//     (scripts/gemm_shapes.py).  The path skips finish(), so a status word
+//     would never be written; the host (gpbs_hip_gemm_bf16) therefore selects
+//     it for direct calls alone, and a runner's launch, which always carries
+//     its status word, keeps the queue whatever the opts say.  Measured
 //     (profiles/r6/s61_gemm_shapes.jsonl): 4096^3 0.1130 -> 0.1052 ms (1216 ->
 //     1306 TF/s; torch.mm 1475 on that box).  The queue costs ~8 us per launch:
 //     each workgroup waits on three device-scope atomics with returns (its
@@ -710,7 +714,8 @@ int gpbs_hip_gemm_bf16(const void* A, const void* Bt, void* C, int M, int N, int
     const u32 miss = (u32)((((u64)M + N) * K * 2 / 128) / ntiles + (u64)G2_BM * G2_BM * 2 / 128);
     const u32 m2 = mode | ((g_gemm_opts & 1) ? kGemmXRange : 0u) |
                    ((g_gemm_opts & 8) && ntiles % kXcds == 0 ? kGemmBlock2D : 0u) |
-                   ((g_gemm_opts & (1 << 23)) && (mode & 3) == GATE_NONE && grid == ntiles ? kGemmStatic : 0u);
+                   ((g_gemm_opts & (1 << 23)) && (mode & 3) == GATE_NONE && grid == ntiles && !status && !cnt
+                        ? kGemmStatic : 0u);
     hipLaunchKernelGGL(k_gemm256_bf16_tn, dim3(grid), dim3(G2_NT), 0, s, (const u16*)A, (const u16*)Bt, (u16*)C, M, N,
                        K, (WorkQueue*)q, (const PartTable*)table, m2, me, (u64*)cnt, inst, refs, miss, (u32*)status);
     return hipGetLastError() == hipSuccess ? 0 : -5;
